@@ -19,6 +19,15 @@ headline instead (``--batch`` images per rank).
 
 Profiling: put rocprofv3 on a single-rank command (`rocprofv3 ... -- python3 bench.py --gpus 1 ...`); with --gpus N > 1 this
 process is only a launcher, so a profiler must wrap the per-rank command, never the launcher.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (``ms_per_step`` = one training
+step + one scoring pass).  ``--full`` adds every side measurement: the start-up self-check at N = 1 (at N > 1 it always runs: it
+decides how the ranks launch), the RCCL / exposed-communication probes, per-kernel rooflines (HIP events around every launch, also
+inside the timed scoring passes), the batch-32 partition, precision 16, bf16x6, end-to-end, the CPU baseline and the WideResNet-50
+member.  ``--dump-outputs DIR`` writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32, 64 MB at most:
+train_loss_acc, train_logits, train_embeddings, train_params_sample (2^20 seeded entries of the updated parameters, OIHW order) and
+anomaly_maps_sample (the 256 x 256 maps of 64 seeded images); under --config wrn50 anomaly_maps_sample holds 16 seeded 512 x 512 maps.
+Inputs and weights are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -83,7 +92,36 @@ def pinned_traffic(pattern, match, sources):
     return None, "no committed PMC pass with this launch geometry"
 
 
-def parse_args():
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def seeded_rows(t, n, seed):
+    """A fixed choice of n entries along dim 0 (seeded, in index order); all of them when there are no more than n."""
+    import torch
+    if t.shape[0] <= n:
+        return t
+    idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return t[idx.to(t.device)]
+
+
+def to_host(t):
+    """A float32 host copy: taken right after the timed steps, before later launches overwrite the step's output buffers."""
+    return t.detach().float().cpu().numpy()
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: name -> float32 array, written as out_dir/<name>.npy; refuses more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -109,7 +147,10 @@ def parse_args():
                     help="32: exact fp32 MFMA (headline); 16: fp16 operands + loss scaling (the reference's Trainer(precision=16)); "
                          "bf16: bf16 operands")
     ap.add_argument("--extras", default="", help="comma list of opt-in side measurements: precision16, bf16, bf16x3, bf16x6")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (the --no-* options above pick among them); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    return ap.parse_args(argv)
 
 
 def launch_ranks(args):
@@ -325,10 +366,11 @@ def end_to_end(args):
     return res
 
 
-def measure_wrn50(args, steps=None, warmup=None):
+def measure_wrn50(args, steps=None, warmup=None, dump=None):
     """BASELINE configs[3]: 64 synthetic 512 x 512 images -> WideResNet-50-2 layer1-3 features -> per-scale cosine 3-NN maps against
     588-row banks -> blur + bilinear 512 x 512, mean over the scales.  One GPU; throughput only (no reference counterpart).
-    Returns the bench object (a full line under --config wrn50, the "wrn50" member of the default line otherwise)."""
+    Returns the bench object (a full line under --config wrn50, the "wrn50" member of the --full line otherwise); `dump`, a dict,
+    receives the maps of the last timed step (a seeded sample of 16)."""
     import torch
     from self_supervised import ops
     from self_supervised.wrn50 import FeatureDistanceScorer, WideResNet50Features
@@ -353,14 +395,16 @@ def measure_wrn50(args, steps=None, warmup=None):
     for _ in range(max(warmup, 1)):
         step()
     torch.cuda.synchronize()
-    ops.PROFILE = []
+    ops.PROFILE = [] if args.full else None          # --full: HIP events around every launch (the roofline below)
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        maps = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof = ops.drain_profile()
     ops.PROFILE = None
+    if dump is not None:
+        dump["anomaly_maps_sample"] = to_host(seeded_rows(maps, 16, 0))
     out = {"metric": "anomaly-maps/sec, WideResNet-50-2 layer1-3 feature-distance maps 512x512 bs64", "unit": "anomaly-maps/sec",
            "n_gpus": 1, "steps": steps, "warmup": warmup, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
            "dtype": "f32", "data": "synthetic",
@@ -372,22 +416,23 @@ def measure_wrn50(args, steps=None, warmup=None):
                                     "(self_supervised/wrn50.py, oracle/wrn50.py)",
                       "images_per_gpu": batch, "bank_rows": 588, "scales": [[128, 256], [64, 512], [32, 1024]]},
            "value": round(batch * steps / dt, 2), "ms_per_step": round(1e3 * dt / steps, 3)}
-    recs = [r for r in prof if r["kernel"].startswith("conv_igemm") or r["kernel"].startswith("conv3x3_fw32")]
-    t = sum(r["ms"] for r in recs) * 1e-3
-    fl = sum(r["flops"] for r in recs)
-    allk = sum(r["ms"] for r in prof) * 1e-3
-    out["roofline"] = {"bound": "mfma", "achieved": round(fl / t / 1e12, 2), "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                       "frac": round(fl / t / 1e12 / PEAK_F32_MFMA_TFLOPS, 4), "traffic": None,
-                       "kernel": "the trunk's convs: conv_igemm_f32_kernel (NHWC: 1 x 1 and stride-2 convs) + conv3x3_hw_kernel<float> (3 x 3 / "
-                                 "stride 1, csrc/conv16w.hip); every FLOP counted is issued, no tap skipping",
-                       "launches": len(recs), "avg_launch_ms": round(1e3 * t / len(recs), 4),
-                       "alg_gflop_per_launch": round(fl / len(recs) / 1e9, 3), "share_of_gpu_time": round(t / allk, 4),
-                       "gflop_per_image": round(sum(r["flops"] for r in prof) / steps / batch / 1e9, 2)}
-    by = {}
-    for r in prof:
-        e = by.setdefault(r["kernel"], [0.0, 0, 0.0]); e[0] += r["ms"]; e[1] += 1; e[2] += r["flops"]
-    out["kernel_ms"] = {k: [round(v[0] / steps, 3), v[1] // steps, round(v[2] / max(v[0], 1e-9) / 1e9, 1)] for k, v in sorted(by.items())}
-    if not args.no_cpu_baseline:
+    if prof:
+        recs = [r for r in prof if r["kernel"].startswith("conv_igemm") or r["kernel"].startswith("conv3x3_fw32")]
+        t = sum(r["ms"] for r in recs) * 1e-3
+        fl = sum(r["flops"] for r in recs)
+        allk = sum(r["ms"] for r in prof) * 1e-3
+        out["roofline"] = {"bound": "mfma", "achieved": round(fl / t / 1e12, 2), "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                           "frac": round(fl / t / 1e12 / PEAK_F32_MFMA_TFLOPS, 4), "traffic": None,
+                           "kernel": "the trunk's convs: conv_igemm_f32_kernel (NHWC: 1 x 1 and stride-2 convs) + conv3x3_hw_kernel<float> (3 x 3 / "
+                                     "stride 1, csrc/conv16w.hip); every FLOP counted is issued, no tap skipping",
+                           "launches": len(recs), "avg_launch_ms": round(1e3 * t / len(recs), 4),
+                           "alg_gflop_per_launch": round(fl / len(recs) / 1e9, 3), "share_of_gpu_time": round(t / allk, 4),
+                           "gflop_per_image": round(sum(r["flops"] for r in prof) / steps / batch / 1e9, 2)}
+        by = {}
+        for r in prof:
+            e = by.setdefault(r["kernel"], [0.0, 0, 0.0]); e[0] += r["ms"]; e[1] += 1; e[2] += r["flops"]
+        out["kernel_ms"] = {k: [round(v[0] / steps, 3), v[1] // steps, round(v[2] / max(v[0], 1e-9) / 1e9, 1)] for k, v in sorted(by.items())}
+    if args.full and not args.no_cpu_baseline:
         cores = host_cores()
         torch.set_num_threads(cores)
         xc = x[:1].cpu()
@@ -405,7 +450,11 @@ def measure_wrn50(args, steps=None, warmup=None):
 
 
 def bench_wrn50(args):
-    print(json.dumps(measure_wrn50(args)))
+    dump = {} if args.dump_outputs else None
+    out = measure_wrn50(args, dump=dump)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
+    print(json.dumps(out))
 
 
 def main():
@@ -496,6 +545,8 @@ def main():
     y = torch.randint(0, 4, (per_rank,), generator=torch.Generator().manual_seed(1235 + rank)).to(dev)
     bank = torch.randn(588, 512, generator=torch.Generator().manual_seed(2)).to(dev)
     use_graph = not args.no_graph
+    full = args.full
+    dump = {} if args.dump_outputs and rank == 0 else None      # --dump-outputs: name -> host array of the last timed step
 
     def barrier():
         torch.cuda.synchronize()
@@ -504,6 +555,7 @@ def main():
             torch.cuda.synchronize()
 
     def timed(fn, steps, warmup):
+        """-> (seconds of `steps` calls of fn, what the last of them returned)"""
         import gc
         for _ in range(warmup):
             fn()
@@ -512,9 +564,10 @@ def main():
         gc.disable()
         try:
             barrier()
+            last = None
             t0 = time.perf_counter()
             for _ in range(steps):
-                fn()
+                last = fn()
             barrier()
             dt = time.perf_counter() - t0
         finally:
@@ -523,7 +576,7 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
-        return dt
+        return dt, last
 
     def optional(name, fn):
         """Side measurements must never take the headline line down with them: on failure they are reported as skipped
@@ -535,12 +588,12 @@ def main():
             return None
 
     res, prof = {}, {}
-    if world > 1:
+    if world > 1 and full:
         res["rccl"] = optional("rccl_probe", rccl_probe)
     extras = [e for e in args.extras.split(",") if e]
     # bf16x6 (every fp32 product formed from three bf16 parts per operand, the six largest partial products, fp32 accumulate: the
     # accuracy of the fp32 MFMA at 6/16 of its matrix time) is measured by default on one GPU beside the exact-fp32 headline
-    faithful = world == 1 and not args.no_faithful and args.train_precision == "32"
+    faithful = full and world == 1 and not args.no_faithful and args.train_precision == "32"
     if faithful and "bf16x6" not in extras:
         extras.append("bf16x6")
     if args.phase in ("both", "train"):
@@ -549,18 +602,24 @@ def main():
         prec = {"32": 32, "16": 16, "bf16": "bf16"}[args.train_precision]
         trainer = training.DataParallelStep(model, lr=0.005, world_size=world, precision=prec, graph=use_graph)
         ops.PROFILE = None
-        # start-up self-check (every N; decisive at N > 1): one eager step and one graph-replayed step from the same state must
-        # leave identical bits, and every rank the same replica -- else all ranks fall back to eager launches and the line says so
-        res["self_check"] = optional("self_check", lambda: trainer.self_check(x, y))
+        # start-up self-check (--full at N = 1; always at N > 1, where it decides): one eager step and one graph-replayed step from the
+        # same state must leave identical bits, and every rank the same replica -- else all ranks fall back to eager launches and the
+        # line says so
+        if full or world > 1:
+            res["self_check"] = optional("self_check", lambda: trainer.self_check(x, y))
         res["launch_mode"] = trainer.launch_mode
         # warm up (eager step, capture), then let the batch live in the recorded step's own input buffer: a producer (the GPU input
         # pipeline) writes there directly, so the timed steps carry no device-to-device copy of the batch
         for _ in range(max(args.warmup, 2)):
             trainer.step(x, y)
         xb, yb = trainer.bind_inputs(x, y)
-        res["train_s"] = timed(lambda: trainer.step(xb, yb), args.steps, 1)
+        res["train_s"], la = timed(lambda: trainer.step(xb, yb), args.steps, 1)
+        if dump is not None:
+            dump.update(train_loss_acc=to_host(la), train_logits=to_host(trainer.last_logits),
+                        train_embeddings=to_host(trainer.last_embeddings),
+                        train_params_sample=to_host(seeded_rows(torch.cat([p.detach().reshape(-1) for p in model.parameters()]), 1 << 20, 0)))
         res["train_graph_segments"] = sum(1 for p in trainer._plans.values() for o in p["ops"] if o[0] == "graph")
-        if world > 1:
+        if world > 1 and full:
             # how much of the gradient all-reduce stays exposed: HIP events around the wait of every step (a few steps outside the
             # timed region: event records are not free), and the bytes each rank puts on the wire per step
             def comm_probe():
@@ -577,12 +636,13 @@ def main():
             res["comm"] = optional("comm_probe", comm_probe)
         # per-kernel attribution: the same step launched eagerly with HIP events around every launch (a captured graph
         # cannot carry them); not part of the timed region above
-        ops.PROFILE = []
-        for _ in range(2):
-            trainer.step(x, y)
-        prof["train"] = ops.drain_profile()
-        prof_train_steps = 2
-        ops.PROFILE = None
+        if full:
+            ops.PROFILE = []
+            for _ in range(2):
+                trainer.step(x, y)
+            prof["train"] = ops.drain_profile()
+            prof_train_steps = 2
+            ops.PROFILE = None
 
         def partition_extra():
             nb = 32 if world == 1 else (args.batch if strong_headline else args.global_batch // world)
@@ -595,11 +655,11 @@ def main():
             for _ in range(3):
                 trainer.step(xs, ys)
             xsb, ysb = trainer.bind_inputs(xs, ys)
-            dt = timed(lambda: trainer.step(xsb, ysb), max(args.steps, 10), 1)
+            dt, _ = timed(lambda: trainer.step(xsb, ysb), max(args.steps, 10), 1)
             return {"images_per_gpu": nb, "global_batch": nb * world, "steps": max(args.steps, 10),
                     "train_images_per_sec": round(world * nb * max(args.steps, 10) / dt, 2),
                     "train_ms_per_step": round(1e3 * dt / max(args.steps, 10), 3)}
-        if not args.no_partition_extra:
+        if full and not args.no_partition_extra:
             r = optional("partition", partition_extra)
             if r:
                 res["partition"] = r
@@ -614,7 +674,7 @@ def main():
             for _ in range(3):                                    # eager step, capture, one replay
                 tx.step(x, y)
             xb16, yb16 = tx.bind_inputs(x, y)
-            dt = timed(lambda: tx.step(xb16, yb16), n, 1)
+            dt, _ = timed(lambda: tx.step(xb16, yb16), n, 1)
             ms = 1e3 * dt / n
             ops.PROFILE = []
             for _ in range(2):
@@ -658,9 +718,9 @@ def main():
                 "kernel_ms_columns": "ms per step, launches per step, TFLOP/s, GB/s (algorithmic bytes of the kernel's operands)"}
             del tx
             return out16
-        # (N = 1 only by default: a second DataParallelStep brings a second capture stream, and with two of them a multi-rank replay
+        # (--full at N = 1 only: a second DataParallelStep brings a second capture stream, and with two of them a multi-rank replay
         # was measured to stall on this runtime -- DESIGN s.6; `--extras precision16` forces it)
-        if args.train_precision == "32" and not args.no_precision16 and (world == 1 or "precision16" in extras):
+        if args.train_precision == "32" and not args.no_precision16 and ((full and world == 1) or "precision16" in extras):
             extras = [e for e in extras if e != "precision16"]
             r16 = optional("precision16", precision16_object)
             if r16:
@@ -673,7 +733,7 @@ def main():
 
             def run_extra(p=pmap[name]):
                 tx = training.DataParallelStep(model, lr=0.005, world_size=world, precision=p, graph=use_graph)
-                return timed(lambda: tx.step(x, y), max(args.steps, 10), 4)       # eager step, capture, two replays, then the clock
+                return timed(lambda: tx.step(x, y), max(args.steps, 10), 4)[0]    # eager step, capture, two replays, then the clock
             dt = optional(name, run_extra)
             if dt:
                 res["train_extra_" + name] = round(world * per_rank * max(args.steps, 10) / dt, 2)
@@ -691,25 +751,29 @@ def main():
         det.fit_bank(bank)
         ops.PROFILE = None
         for i in range(max(args.warmup, 1)):
-            if i == max(args.warmup, 1) - 1:
+            if full and i == max(args.warmup, 1) - 1:
                 # the last warm-up pass runs exactly what the timed passes run, HIP events around every launch included: in the first
                 # process on a fresh box the event path is otherwise executed -- and paged in from the image -- for the first time
                 # inside the timed region (measured: 387.8 ms per pass in the first process of a box, 375.4 in every later one)
                 ops.PROFILE = []
             score_batch(model, det, x, args.size)
         ops.drain_profile()
-        ops.PROFILE = []           # scoring is ~270 launches of ~1.5 ms: the events ride inside the timed region
-        res["score_s"] = timed(lambda: score_batch(model, det, x, args.size), args.steps, 0)
-        prof["score"] = ops.drain_profile()
+        ops.PROFILE = [] if full else None    # --full: scoring is ~270 launches of ~1.5 ms, the events ride inside the timed region
+        res["score_s"], maps = timed(lambda: score_batch(model, det, x, args.size), args.steps, 0)
+        if dump is not None:
+            dump["anomaly_maps_sample"] = to_host(seeded_rows(maps, 64, 0))
+        del maps
+        if full:
+            prof["score"] = ops.drain_profile()
         ops.PROFILE = None
-        if world == 1 and per_rank > 32 and not args.no_partition_extra:
+        if full and world == 1 and per_rank > 32 and not args.no_partition_extra:
             # scoring side of the 8-GPU strong partition: 32 images = 26 912 patches per rank
             def score32():
                 xs = x[:32].contiguous()
                 d32 = AnomalyDetector(patch_level=True, batch=32, num_patches=841)
                 d32.fit_bank(bank)
                 n = max(args.steps, 5)
-                dt = timed(lambda: score_batch(model, d32, xs, args.size), n, 1)
+                dt, _ = timed(lambda: score_batch(model, d32, xs, args.size), n, 1)
                 return {"anomaly_maps_per_sec": round(32 * n / dt, 2), "score_ms_per_step": round(1e3 * dt / n, 3), "steps": n}
             res["score32"] = optional("batch-32 scoring", score32)
         if "bf16x6" in extras:                 # how far the bf16x6 maps are from the exact-fp32 ones on this very batch
@@ -727,7 +791,7 @@ def main():
                 os.environ["SSAD_MATH"] = tag
 
                 def run_score_extra():
-                    return timed(lambda: score_batch(model, det, x, args.size), args.steps, 1)
+                    return timed(lambda: score_batch(model, det, x, args.size), args.steps, 1)[0]
                 dt = optional("score_" + tag, run_score_extra)
                 if dt:
                     res["score_extra_" + tag] = round(world * per_rank * args.steps / dt, 3)
@@ -912,13 +976,13 @@ def main():
                 e = by.setdefault(r["kernel"], [0.0, 0, 0.0]); e[0] += r["ms"]; e[1] += 1; e[2] += r["flops"]
             out["kernel_ms"][ph] = {k: [round(v[0] / nst, 3), v[1] // nst,
                                         round(v[2] / max(v[0], 1e-9) / 1e9, 1)] for k, v in sorted(by.items())}
-    if not args.no_e2e and world == 1 and args.phase in ("both", "train"):
+    if full and not args.no_e2e and world == 1 and args.phase in ("both", "train"):
         r = optional("end_to_end", lambda: end_to_end(args))
         if r:
             out["end_to_end"] = r
-    if not args.no_cpu_baseline and world == 1:
+    if full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args)
-    if world == 1 and not args.no_wrn50 and args.phase == "both":
+    if full and world == 1 and not args.no_wrn50 and args.phase == "both":
         model = det = trainer = None
         torch.cuda.empty_cache()
         w50 = optional("wrn50", lambda: measure_wrn50(args, steps=max(min(args.steps, 10), 3), warmup=2))
@@ -926,6 +990,8 @@ def main():
             for k in ("n_gpus", "higher_is_better", "scaling", "vs_baseline", "data"):
                 w50.pop(k, None)
             out["wrn50"] = w50
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

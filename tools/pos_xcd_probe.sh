@@ -44,7 +44,7 @@ PY
     cd /tmp && export TMPDIR=/tmp
     for c in FETCH_SIZE WRITE_SIZE; do
       rm -rf /tmp/prof_${c}_$mode
-      timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/prof_${c}_$mode -o c -- python3 $R/bench.py --phase score --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --no-faithful --no-partition-extra > /tmp/prof_${c}_$mode.json 2> /tmp/prof_${c}_$mode.err || { tail -5 /tmp/prof_${c}_$mode.err; exit 1; }
+      timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/prof_${c}_$mode -o c -- python3 $R/bench.py --full --phase score --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --no-faithful --no-partition-extra > /tmp/prof_${c}_$mode.json 2> /tmp/prof_${c}_$mode.err || { tail -5 /tmp/prof_${c}_$mode.err; exit 1; }
     done
     python3 $R/tools/traffic_json.py /tmp/prof_FETCH_SIZE_$mode /tmp/prof_WRITE_SIZE_$mode $OUT/r04_traffic_lpt$mode.json 107648
   fi

@@ -4,7 +4,7 @@
 #   bash tools/profile_p16.sh r05   -> gpurun_out/<tag>_p16_*  (copy the summaries into profiles/)
 TAG=${1:-r06}
 R=$PWD; OUT=$R/gpurun_out; cd /tmp && export TMPDIR=/tmp
-ARGS="--phase train --train-precision 16 --no-cpu-baseline --no-e2e --no-wrn50 --no-partition-extra --no-faithful"
+ARGS="--full --phase train --train-precision 16 --no-cpu-baseline --no-e2e --no-wrn50 --no-partition-extra --no-faithful"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p16_stats -o s -- python3 $R/bench.py $ARGS --steps 10 --warmup 3 > $OUT/${TAG}_p16_bench_line_under_rocprof.json 2> /tmp/p16_stats.err || { tail -5 /tmp/p16_stats.err; exit 1; }
 cp $(find /tmp/p16_stats -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_p16_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

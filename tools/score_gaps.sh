@@ -5,7 +5,7 @@
 R=$PWD; OUT=$R/gpurun_out; cd /tmp; export TMPDIR=/tmp
 for run in first second; do
   rm -rf /tmp/sg_$run
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/sg_$run -o s -- python3 $R/bench.py --phase score --no-cpu-baseline --no-e2e --no-wrn50 --no-partition-extra --no-faithful --steps 5 --warmup 3 > /tmp/sg_$run.json 2>/tmp/sg_$run.err || { tail -5 /tmp/sg_$run.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/sg_$run -o s -- python3 $R/bench.py --full --phase score --no-cpu-baseline --no-e2e --no-wrn50 --no-partition-extra --no-faithful --steps 5 --warmup 3 > /tmp/sg_$run.json 2>/tmp/sg_$run.err || { tail -5 /tmp/sg_$run.err; exit 1; }
   RUN=$run python3 - <<'PY'
 import csv, glob, os, json
 run = os.environ['RUN']
