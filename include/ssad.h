@@ -122,11 +122,16 @@ int ssad_patch_gather_hwnc(const float* dense, float* out, int64_t B, int prow, 
 int ssad_patch_gather_hwnc_band(const float* dense, float* out, int64_t B, int prow, int pcol, int shift, int Hd, int Wd, int C,
                                 int H, int W, int lo, int hi, int ilo, int ihi, void* stream);
 
-/* Which exact-fp32 instantiation ssad_conv_igemm_fwd (hwnc = 0) / ssad_conv_igemm_fwd_hwnc (hwnc = 1) gives a problem:
- * BM * 100000 + BN * 100 + BK of the workgroup tile, negated when its rows are position-major (hwnc = 2: the tile of a
- * ssad_conv_igemm_fwd_hwnc_ring launch).  Measurement aid only
- * (bench.py names the instantiations its roofline figure sums over); no reference counterpart. */
-int ssad_conv_igemm_tile(int64_t N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int hwnc);
+/* Which exact-fp32 instantiation an implicit-GEMM entry point gives a problem: BM * 100000 + BN * 100 + BK of the workgroup
+ * tile, negated when its rows are position-major.  mode: 0 ssad_conv_igemm_fwd, 1 ssad_conv_igemm_fwd_hwnc,
+ * 2 ssad_conv_igemm_fwd_hwnc_ring, 3 ssad_conv_igemm_fwd_stats, 4 ssad_conv_igemm_dgrad / _dgrad_masked.  The arguments are
+ * always the forward conv's (mode 4: x [N][H][W][Cin] -> y [N][Ho][Wo][Cout] at stride 1 or 2, the gradient flowing back to x).
+ * Host-only (no GPU needed).  Measurement and test aid (bench.py names the instantiations its roofline figure sums over;
+ * tests/test_igemm_tile_table.py pins the selection); no reference counterpart. */
+int ssad_conv_igemm_tile(int64_t N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int mode);
+/* The same choice as the IgemmTile value of csrc/conv_igemm.hip (0 .. 12), + 100 when the rows are position-major: tells apart
+ * the instantiations that share a BM / BN / BK (single- and double-buffered, four-wave 256 x 128). */
+int ssad_conv_igemm_tile_id(int64_t N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int mode);
 
 /* Replaces F.adaptive_avg_pool2d(., (1,1)) + flatten + torch.cat (models.py:227-245):
  * out[n*out_stride + out_offset + c] = mean over HW of in[n][hw][c]. */

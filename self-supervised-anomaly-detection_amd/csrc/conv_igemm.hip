@@ -1192,6 +1192,34 @@ int dispatch(const ConvParams& p, hipStream_t st) {
     }
 }
 
+// Entry points as ssad_conv_igemm_tile numbers them (its `mode` argument, include/ssad.h)
+enum IgemmEntry { E_FWD = 0, E_HWNC = 1, E_RING = 2, E_STATS = 3, E_DGRAD = 4 };
+
+// Whether a launch's rows are position-major (POS = true).  [H][W][N][C] tensors always are: it is what makes a workgroup's rows
+// contiguous.  NHWC forward convs are when padding is a visible share of the taps (small maps, many samples), except under the
+// statistics epilogue, whose column sums are sized for pixel-major row tiles (ssad_conv_stats_workspace).  Input gradients never are.
+// conv_fwd_impl, dgrad_impl and ssad_conv_igemm_tile all decide here, so the reporter names the tile the dispatch runs.
+static bool posmajor_rows(IgemmEntry e, const ConvParams& p) {
+    if (e == E_HWNC || e == E_RING) return true;
+    return e == E_FWD && p.pad > 0 && p.N >= 128 && p.Ho * p.Wo <= 4;
+}
+
+// The problem an input gradient hands to the forward kernel: dy [N][Hy][Wy][Cout] gathered through the flipped filter into
+// dx [N][Hx][Wx][Cin] (contraction over Cout, the kernel's columns are dx's Cin channels, stride 1 with pad KH-1-pad; the stride-2
+// form is the TS = 2 instantiation over the same rows)
+static ConvParams dgrad_params(int64_t N, int Hy, int Wy, int Cout, int Hx, int Wx, int Cin, int KH, int KW, int pad) {
+    ConvParams p;
+    p.pos_lpt = 0; p.pos_sg = 0; p.pos_chunk = 1;
+    p.skip_lo = 1; p.skip_hi = 0;
+    p.in = nullptr; p.wt = nullptr; p.out = nullptr; p.scale = nullptr; p.shift = nullptr; p.residual = nullptr; p.res_mask = nullptr;
+    p.H = Hy; p.W = Wy; p.Cin = Cout; p.Cout = Cin; p.KH = KH; p.KW = KW; p.relu = 0;
+    p.stride = 1; p.pad = KH - 1 - pad; p.N = N; p.hwnc = 0;
+    p.Ho = Hx; p.Wo = Wx; p.stats = nullptr;
+    p.M = N * Hx * Wx;
+    p.K = KH * KW * Cout;
+    return p;
+}
+
 // buffer-load staging (IGEMM_BUFLD): the rows of a tile -- up to 256 consecutive output pixels, i.e. 256 / (Ho Wo) + 2 input images, or
 // 256 samples of a position-major launch -- are addressed by 32-bit byte offsets from the tile's first image
 static bool tile_span_ok(const ConvParams& p, bool posmajor, int elt_bytes, int ts = 1) {
@@ -1228,9 +1256,7 @@ int conv_fwd_impl(const float* in, const float* w_ohwi, float* out, const float*
     p.K = KH * KW * Cin;
     p.hwnc = hwnc;
     p.stats = stats;
-    // position-major rows pay off when padding is a visible share of the taps (small maps, many samples); in the
-    // [H][W][N][C] layout they are also what makes a workgroup's rows contiguous
-    const bool posmajor = hwnc || (!stats && pad > 0 && N >= 128 && p.Ho * p.Wo <= 4);
+    const bool posmajor = posmajor_rows(hwnc ? (skip_lo <= skip_hi ? E_RING : E_HWNC) : stats ? E_STATS : E_FWD, p);
     SSAD_CHECK_ARG(cdiv64(p.M, 128) + 32 * p.Ho * p.Wo < (int64_t)2147483647, "M too large for one launch");
     SSAD_CHECK_ARG(tile_span_ok(p, posmajor, io16 ? 2 : 4), "input images too large: the rows of a tile must span less than 2 GB");
     hipStream_t st = (hipStream_t)stream;
@@ -1336,21 +1362,33 @@ extern "C" int ssad_conv_igemm_fwd_hwnc_ring(const float* in, const float* w_ohw
                          nullptr, 0, skip_lo, skip_hi);
 }
 
-// Which instantiation ssad_conv_igemm_fwd (hwnc = 0) / ssad_conv_igemm_fwd_hwnc (hwnc = 1) runs a problem on, as
-// BM * 100000 + BN * 100 + BK, negative when the rows are position-major (POS): what bench.py's roofline object names.
-extern "C" int ssad_conv_igemm_tile(int64_t N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int hwnc) {
+// Which instantiation an exact-fp32 launch runs a problem on: the IgemmTile value, + 100 when the rows are position-major (POS).
+// mode = the entry point (IgemmEntry: 0 ssad_conv_igemm_fwd, 1 _fwd_hwnc, 2 _fwd_hwnc_ring, 3 _fwd_stats, 4 _dgrad / _dgrad_masked);
+// the shape is always the forward conv's (for mode 4: x [N][H][W][Cin] -> y [N][Ho][Wo][Cout], stride 1 or 2).
+extern "C" int ssad_conv_igemm_tile_id(int64_t N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int mode) {
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     ConvParams p;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-    p.skip_lo = hwnc == 2 ? 0 : 1; p.skip_hi = 0;          // hwnc = 2: a ring launch (ssad_conv_igemm_fwd_hwnc_ring)
-    p.Ho = (H + 2 * pad - KH) / stride + 1;
-    p.Wo = (W + 2 * pad - KW) / stride + 1;
-    p.M = N * p.Ho * p.Wo;
-    const bool posmajor = hwnc || (pad > 0 && N >= 128 && p.Ho * p.Wo <= 4);
+    if (mode == E_DGRAD) {
+        p = dgrad_params(N, Ho, Wo, Cout, H, W, Cin, KH, KW, pad);
+    } else {
+        p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
+        p.skip_lo = mode == E_RING ? 0 : 1; p.skip_hi = 0;          // a ring launch: any non-empty skipped square
+        p.Ho = Ho; p.Wo = Wo;
+        p.M = N * p.Ho * p.Wo;
+    }
+    if (posmajor_rows((IgemmEntry)mode, p)) return 100 + (int)pick_tile<true>(p);
+    const IgemmTile t = pick_tile<false>(p);
+    return t == T_256x256 ? T_128x128 : (int)t;                 // (dispatch: 256 x 256 is position-major only)
+}
+
+// The same as BM * 100000 + BN * 100 + BK of the workgroup tile, negative when its rows are position-major: what bench.py's
+// roofline object names.
+extern "C" int ssad_conv_igemm_tile(int64_t N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int mode) {
     static const int dims[13][3] = {{256, 64, 16}, {256, 64, 32}, {128, 64, 32}, {256, 128, 32}, {256, 128, 32}, {128, 256, 32},
                                     {64, 64, 32}, {128, 128, 32}, {256, 256, 32}, {128, 64, 32}, {128, 64, 16}, {128, 128, 16}, {128, 256, 16}};
-    const int t = posmajor ? (int)pick_tile<true>(p) : (int)pick_tile<false>(p);
+    const int id = ssad_conv_igemm_tile_id(N, H, W, Cin, Cout, KH, KW, stride, pad, mode), t = id % 100;
     const int code = dims[t][0] * 100000 + dims[t][1] * 100 + dims[t][2];
-    return posmajor ? -code : code;
+    return id >= 100 ? -code : code;
 }
 
 // dgrad: dx[n][iy][ix][ci] = sum_{ky,kx,co} dy[n][(iy+pad-ky)/s][(ix+pad-kx)/s][co] * w[co][ky][kx][ci] (+ residual).
@@ -1370,16 +1408,10 @@ static int dgrad_impl(const float* dy, const float* w_flipT, float* dx, const fl
     SSAD_CHECK_ARG(stride == 1 || stride == 2, "stride 1 or 2");
     SSAD_CHECK_ARG((Hx + 2 * pad - KH) / stride + 1 == Hy && (Wx + 2 * pad - KW) / stride + 1 == Wy, "dy/dx sizes disagree");
     SSAD_CHECK_ARG(KH == KW && KH * KW <= 32, "square filters with at most 32 taps only");
-    ConvParams p;
-    p.pos_lpt = 0; p.pos_sg = 0; p.pos_chunk = 1;
-    p.skip_lo = 1; p.skip_hi = 0;
     SSAD_CHECK_ARG(!res_mask || (residual && Cin % 4 == 0), "residual mask needs a residual and Cin % 4 == 0");
-    p.in = dy; p.wt = w_flipT; p.out = dx; p.scale = nullptr; p.shift = nullptr; p.residual = residual; p.res_mask = res_mask;
-    p.H = Hy; p.W = Wy; p.Cin = Cout; p.Cout = Cin; p.KH = KH; p.KW = KW; p.relu = 0;
-    p.stride = 1; p.pad = KH - 1 - pad; p.N = N; p.hwnc = 0;
-    p.Ho = Hx; p.Wo = Wx; p.stats = nullptr;
-    p.M = N * Hx * Wx;
-    p.K = KH * KW * Cout;
+    ConvParams p = dgrad_params(N, Hy, Wy, Cout, Hx, Wx, Cin, KH, KW, pad);
+    p.in = dy; p.wt = w_flipT; p.out = dx; p.residual = residual; p.res_mask = res_mask;
+    SSAD_CHECK_ARG(!posmajor_rows(E_DGRAD, p), "input gradients: pixel-major rows");
     SSAD_CHECK_ARG(cdiv64(p.M, 128) < (int64_t)2147483647, "M too large for one launch");
     SSAD_CHECK_ARG(tile_span_ok(p, false, io16 ? 2 : 4, stride), "gradient images too large: the rows of a tile must span less than 2 GB");
     hipStream_t st = (hipStream_t)stream;

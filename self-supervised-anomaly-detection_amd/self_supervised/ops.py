@@ -105,15 +105,40 @@ def _inbounds_taps(h, w, kh, kw, stride, pad):
     return ny * nx
 
 
-def igemm_tile_name(n, h, w, cin, cout, kh, kw, stride, pad, hwnc):
-    """Template arguments of the exact-fp32 implicit-GEMM instantiation a problem runs on (csrc/conv_igemm.hip: BM, BN, TM, TN, BK)."""
-    if not hwnc and kh == kw == h == w == 1 and n <= _hip.lib().ssad_linear_small_max_rows():
+IGEMM_FWD, IGEMM_HWNC, IGEMM_RING, IGEMM_STATS, IGEMM_DGRAD = range(5)     # ssad_conv_igemm_tile(_id) modes (include/ssad.h)
+
+
+# IgemmTile (csrc/conv_igemm.hip) in enum order: short name -> template arguments BM, BN, TM, TN, BK, DB (two LDS stages)
+IGEMM_TILES = [("256x64_K16", (256, 64, 2, 2, 16, True)), ("256x64_SB", (256, 64, 2, 2, 32, False)),
+               ("128x64", (128, 64, 1, 2, 32, True)), ("256x128", (256, 128, 2, 2, 32, True)),
+               ("256x128_W4", (256, 128, 4, 2, 32, True)), ("128x256", (128, 256, 2, 4, 32, True)),
+               ("64x64", (64, 64, 1, 1, 32, True)), ("128x128", (128, 128, 2, 2, 32, True)),
+               ("256x256", (256, 256, 4, 4, 32, True)), ("128x64_SB", (128, 64, 1, 2, 32, False)),
+               ("128x64_K16", (128, 64, 1, 2, 16, True)), ("128x128_K16", (128, 128, 2, 2, 16, True)),
+               ("128x256_K16", (128, 256, 2, 4, 16, True))]
+LINEAR_SMALL = "linear_small"
+
+
+def igemm_tile(n, h, w, cin, cout, kh, kw, stride, pad, mode):
+    """(short tile name, position-major) of the exact-fp32 implicit-GEMM launch of a problem (ssad_conv_igemm_tile_id).  The shape
+    is the forward conv's; mode is the entry point (IGEMM_*: IGEMM_DGRAD = the input gradient of that conv).  1 x 1 layers over
+    1 x 1 maps with few rows go to csrc/linear_small.hip instead: (LINEAR_SMALL, False)."""
+    k = cout if mode == IGEMM_DGRAD else cin
+    if (mode in (IGEMM_FWD, IGEMM_STATS, IGEMM_DGRAD) and kh == kw == h == w == 1 and stride == 1 and pad == 0 and k % 4 == 0
+            and n <= _hip.lib().ssad_linear_small_max_rows()):
+        return LINEAR_SMALL, False
+    t = _hip.lib().ssad_conv_igemm_tile_id(n, h, w, cin, cout, kh, kw, stride, pad, int(mode))
+    return IGEMM_TILES[t % 100][0], t >= 100
+
+
+def igemm_tile_name(n, h, w, cin, cout, kh, kw, stride, pad, mode):
+    """Template arguments of that launch (csrc/conv_igemm.hip launch<BM, BN, TM, TN, BK, TS, POS[, DB]>)."""
+    name, pos = igemm_tile(n, h, w, cin, cout, kh, kw, stride, pad, mode)
+    if name == LINEAR_SMALL:
         return "<linear_small: 32 x 32 tiles, csrc/linear_small.hip>"
-    code = _hip.lib().ssad_conv_igemm_tile(n, h, w, cin, cout, kh, kw, stride, pad, int(hwnc))
-    pos, code = code < 0, abs(code)
-    bm, bn, bk = code // 100000, code // 100 % 1000, code % 100
-    tm, tn = {(256, 64): (2, 2), (128, 64): (1, 2), (256, 128): (2, 2), (128, 256): (2, 4), (64, 64): (1, 1)}.get((bm, bn), (2, 2))
-    return f"<{bm},{bn},{tm},{tn},{bk},1,{'true' if pos else 'false'}>"
+    bm, bn, tm, tn, bk, db = dict(IGEMM_TILES)[name]
+    ts = stride if mode == IGEMM_DGRAD else 1
+    return f"<{bm},{bn},{tm},{tn},{bk},{ts},{'true' if pos else 'false'}{'' if db else ',false'}>"
 
 
 def _kname(base, mode):
@@ -292,7 +317,7 @@ def conv_fwd_hwnc(x, w_ohwi, scale=None, shift=None, residual=None, relu=False, 
                                                      _hip.ptr(shift, True), _hip.ptr(residual, True), int(relu), n, h, w,
                                                      cin, cout, kh, kw, stride, pad, _hip.stream()),
          exec_flops=2.0 * n * cout * cin * _inbounds_taps(h, w, kh, kw, stride, pad) if PROFILE is not None else None,
-         tile=lambda: igemm_tile_name(n, h, w, cin, cout, kh, kw, stride, pad, 1))
+         tile=lambda: igemm_tile_name(n, h, w, cin, cout, kh, kw, stride, pad, IGEMM_HWNC))
     return out
 
 
@@ -311,7 +336,7 @@ def conv_fwd_hwnc_ring(x, w_ohwi, scale, shift, residual, relu, skip_lo, skip_hi
                                                           _hip.ptr(shift, True), _hip.ptr(residual, True), int(relu), n, h, w,
                                                           cin, cout, 3, 3, 1, 1, skip_lo, skip_hi, _hip.stream()),
          exec_flops=2.0 * n * cout * cin * taps if PROFILE is not None else None,
-         tile=lambda: igemm_tile_name(n, h, w, cin, cout, 3, 3, 1, 1, 2))
+         tile=lambda: igemm_tile_name(n, h, w, cin, cout, 3, 3, 1, 1, IGEMM_RING))
     return out
 
 
@@ -379,7 +404,7 @@ def conv_fwd_stats(x, w_ohwi, eps, momentum, running_mean, running_var, stride=1
                                                stride, pad, int(bf16), eps, momentum, _hip.ptr(mean), _hip.ptr(invstd),
                                                _hip.ptr(running_mean, True), _hip.ptr(running_var, True), ws.data_ptr(),
                                                _hip.stream()),
-         tile=None if bf16 else (lambda: igemm_tile_name(n, h, w, cin, cout, kh, kw, stride, pad, 0)))
+         tile=None if bf16 else (lambda: igemm_tile_name(n, h, w, cin, cout, kh, kw, stride, pad, IGEMM_STATS)))
     return out, mean, invstd
 
 
@@ -757,8 +782,7 @@ def conv_dgrad(dy, w_flipT, x_shape, stride, pad, residual=None, bf16=False, res
              lambda: _hip.lib().ssad_conv_igemm_dgrad_masked(_hip.ptr(dy), _hip.ptr(w_flipT), _hip.ptr(dx), _hip.ptr(residual),
                                                              res_mask.data_ptr(), n, hy, wy, cout, x_shape[1], x_shape[2], cin, kh,
                                                              kw, stride, pad, _hip.stream()),
-             tile=lambda: igemm_tile_name(n, x_shape[1], x_shape[2], cout, cin, kh, kw, 1, kh - 1 - pad, 0).replace(
-                 ",1,false>", f",{stride},false>"))
+             tile=lambda: igemm_tile_name(n, x_shape[1], x_shape[2], cin, cout, kh, kw, stride, pad, IGEMM_DGRAD))
         return dx
     fn = (_hip.lib().ssad_conv_igemm_dgrad_x6 if bf16 == 6 else _hip.lib().ssad_conv_igemm_dgrad_x3 if bf16 == 3 else
           _hip.lib().ssad_conv_igemm_dgrad_f16 if bf16 == 2 else
@@ -768,8 +792,7 @@ def conv_dgrad(dy, w_flipT, x_shape, stride, pad, residual=None, bf16=False, res
          4.0 * (dy.numel() + dx.numel() * (2 if residual is not None else 1) + w_flipT.numel()),
          lambda: fn(_hip.ptr(dy), _hip.ptr(w_flipT), _hip.ptr(dx), _hip.ptr(residual, True), n, hy, wy, cout, x_shape[1],
                     x_shape[2], cin, kh, kw, stride, pad, _hip.stream()),
-         tile=None if bf16 else (lambda: igemm_tile_name(n, x_shape[1], x_shape[2], cout, cin, kh, kw, 1, kh - 1 - pad, 0).replace(
-             ",1,false>", f",{stride},false>")))
+         tile=None if bf16 else (lambda: igemm_tile_name(n, x_shape[1], x_shape[2], cin, cout, kh, kw, stride, pad, IGEMM_DGRAD)))
     return dx
 
 

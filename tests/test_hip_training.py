@@ -796,11 +796,17 @@ def test_rccl_bucketed_allreduce_single_rank(dev, seeded_sd):
 # round 2: kernels at the grid sizes bench.py times, the step at the benchmark batch, fp16 operands
 # ---------------------------------------------------------------------------------------------
 def test_large_grid_conv_dgrad_wgrad(dev):
-    """Shapes whose 128x128 tiling has >= 500 workgroups, i.e. the `launch<128,128,2,2,32>` fp32 instantiation that the
-    bs256 benchmark runs on layers 2-4 (the small-grid switch sends every smaller case to the 128x64 tile): plain conv,
-    the BN-statistics epilogue, dgrad (stride 1 and the parity-class stride-2 form) and the cost-model wgrad splits."""
+    """Shapes whose 128x128 tiling has >= 500 workgroups, the large grids of the bs256 benchmark's layers 2-4: plain conv, the
+    BN-statistics epilogue, dgrad (stride 1 and the parity-class stride-2 form) and the cost-model wgrad splits.  Where Cout is a
+    multiple of 256 the wide tile takes them (`launch<128,256,2,4,16>`, 16-float K-steps: SSAD_CONV256_K16 = 2), elsewhere
+    `launch<128,128,2,2,32>`; the tiles are asserted so that a threshold change cannot move these cases silently (every tile
+    of every entry point: tests/test_hip_igemm_tiles.py)."""
     from self_supervised import ops
+    tiles = {64: ("128x128", "128x128"), 128: ("128x256_K16", "128x128"), 160: ("128x256_K16", "128x256_K16")}   # (forward, dgrad)
     for (n, h, cin, cout, k, s, p) in [(64, 32, 128, 128, 3, 1, 1), (128, 32, 128, 256, 3, 2, 1), (160, 16, 256, 256, 3, 1, 1)]:
+        assert ops.igemm_tile(n, h, h, cin, cout, k, k, s, p, ops.IGEMM_FWD) == (tiles[n][0], False)
+        assert ops.igemm_tile(n, h, h, cin, cout, k, k, s, p, ops.IGEMM_STATS) == (tiles[n][0], False)
+        assert ops.igemm_tile(n, h, h, cin, cout, k, k, s, p, ops.IGEMM_DGRAD) == (tiles[n][1], False)
         g = torch.Generator().manual_seed(n + cout)
         x = torch.randn(n, cin, h, h, generator=g, requires_grad=True)
         wt = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).requires_grad_()
