@@ -379,3 +379,6 @@ class AnomalyDetector:
         if self.patch_level:
             anomaly_scores = torch.reshape(anomaly_scores, (self.batch, 1, self.dim, self.dim))
         return anomaly_scores
+
+
+from .density import GaussianDensityDetector  # noqa: E402,F401  (opt-in second scorer: Ledoit-Wolf Gaussian, Mahalanobis distance)

@@ -668,6 +668,31 @@ def cosine_knn_fused(x, bank_n, k=3):
     return out
 
 
+def gaussian_fit_stats(x, normalize=True):
+    """x [N][D] fp32 -> (mean [D], scatter [D][D], m4 [1]) fp64 of its rows (L2-normalised first when `normalize`): the centred
+    sufficient statistics of a Ledoit-Wolf Gaussian fit (csrc/gde.hip), deterministic."""
+    n, d = x.shape
+    mean = torch.empty(d, device=x.device, dtype=torch.float64)
+    scatter = torch.empty(d, d, device=x.device, dtype=torch.float64)
+    m4 = torch.empty(1, device=x.device, dtype=torch.float64)
+    f64 = torch.float64
+    _run("gaussian_fit_stats", 2.0 * n * d * (d + 1) / 2 + 6.0 * n * d, 4.0 * x.numel() * (1 + (d + 63) // 64) + 8.0 * d * d,
+         lambda: _hip.lib().ssad_gaussian_fit_stats(_hip.ptr(x), n, d, int(bool(normalize)), _hip.ptr(mean, dtype=f64),
+                                                    _hip.ptr(scatter, dtype=f64), _hip.ptr(m4, dtype=f64), _hip.stream()))
+    return mean, scatter, m4
+
+
+def mahalanobis_fused(x, mu_hi, mu_lo, w, normalize=True):
+    """x [N][D] fp32 -> [N] ||W (x_n - mu)||_2 with mu = mu_hi + mu_lo (fp32 pair) and W [D][D] lower triangular, one kernel
+    (csrc/gde.hip); rows L2-normalised first when `normalize`.  FLOPs: the dense 2 N D^2 (the kernel skips W's zero blocks)."""
+    n, d = x.shape
+    out = _new((n,), x)
+    _run("mahalanobis_fused", 2.0 * n * d * d, 4.0 * (x.numel() + w.numel() + 2 * d + n),
+         lambda: _hip.lib().ssad_mahalanobis_fused(_hip.ptr(x), _hip.ptr(mu_hi), _hip.ptr(mu_lo), _hip.ptr(w), _hip.ptr(out), n, d,
+                                                   int(bool(normalize)), _hip.stream()))
+    return out
+
+
 def blur_relu_bilinear(maps, ksize=7, target=256):
     n, c, h, w = maps.shape
     out = _new((n, c, target, target), maps)

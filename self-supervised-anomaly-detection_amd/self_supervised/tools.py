@@ -17,7 +17,7 @@ from . import metrics as mtr
 from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
-from .models import AnomalyDetector, PeraNet
+from .models import AnomalyDetector, GaussianDensityDetector, PeraNet
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -353,9 +353,21 @@ def _mark(name):
         TIMELINE.append((name, time.perf_counter()))
 
 
+DETECTORS = ('knn', 'gde')
+
+
+def _check_detector(detector):
+    if detector not in DETECTORS:
+        raise ValueError(f"detector must be one of {DETECTORS}, got {detector!r}")
+    return detector
+
+
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
-              patch_localization: bool = False) -> ModelOutputsContainer:
-    """tools.py:310-390."""
+              patch_localization: bool = False, detector: str = 'knn') -> ModelOutputsContainer:
+    """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
+    estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows, so
+    patch level only -- the image-level bank is one embedding, quirk Q3)."""
+    scorer = _check_detector(detector)
     del TIMELINE[:]
     print('>>> initializing inference')
     # MVTec test data: file lists and decode threads start BEFORE the checkpoint is read, so that the first group of images is
@@ -430,10 +442,11 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         output.from_list(predictions)
         n_pred = len(predictions)
     print('>>> anomaly detection phase')
+    kind = GaussianDensityDetector if scorer == 'gde' else AnomalyDetector
     if patch_localization:
-        detector = AnomalyDetector(patch_level=True, batch=n_pred, num_patches=model.num_patches)
+        detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches)
     else:
-        detector = AnomalyDetector()
+        detector = kind()
     if model.memory_bank.shape[0] > 1000:            # quirk Q3: the bank is capped at 1000 rows, so this never holds
         normality = model.memory_bank
     elif bank_file is not None and getattr(output, "extra_embeddings", None) is not None:
@@ -468,13 +481,22 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         output_normality.to_cpu()
         normality = output_normality.embedding_vectors
     output.to_cpu()
+    if scorer == 'gde':
+        GaussianDensityDetector.fit_rows(int(normality.shape[0]))      # on every rank, before anybody waits for a broadcast
     if world > 1:
-        # one bank for everybody: rank 0 draws the 70/30 split and fits, the others receive (bank, threshold)
+        # one bank for everybody: rank 0 draws the 70/30 split and fits, the others receive (bank, threshold) -- (state, threshold)
+        # of the Gaussian for 'gde'
         if rank == 0:
             detector.fit(normality)
-        state = broadcast_bank((detector.bank.cpu(), detector.threshold) if rank == 0 else None)
+            payload = (detector.state() if scorer == 'gde' else detector.bank.cpu(), detector.threshold)
+        state = broadcast_bank(payload if rank == 0 else None)
         if rank != 0:
-            detector.bank, detector.threshold = AnomalyDetector._dev(state[0]), state[1]
+            if scorer == 'gde':
+                detector = GaussianDensityDetector.from_state(state[0], patch_level=detector.patch_level, batch=detector.batch,
+                                                              num_patches=detector.dim ** 2 if detector.dim else None)
+                detector.threshold = state[1]
+            else:
+                detector.bank, detector.threshold = AnomalyDetector._dev(state[0]), state[1]
     else:
         detector.fit(normality)
     _mark("bank-fitted")
@@ -524,12 +546,14 @@ def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64)
 
 def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = (256, 256), patch_localization: bool = True,
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
-          metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True):
+          metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
+          detector: str = 'knn'):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
-    category.  Returns the pandas DataFrame (identical on every rank)."""
+    category.  Returns the pandas DataFrame (identical on every rank).  `detector` as in `inference` ('knn' or 'gde')."""
+    _check_detector(detector)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows = {}
@@ -542,7 +566,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
                          batch_size=batch_size, projection_training_params=projection_training_params,
                          fine_tune_params=fine_tune_params, trainer_kwargs=trainer_kwargs)
             out = inference(sub_out + 'best_model.ckpt', data, subject, mvtec_inference=True,
-                            patch_localization=patch_localization)
+                            patch_localization=patch_localization, detector=detector)
         if patch_localization:
             out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False)      # stays on the device: the Evaluator's GPU metrics
         ev = Evaluator(evaluation_metrics=[m for m in metrics if (m != 'f1-score') == patch_localization or m == 'auroc'])
