@@ -469,6 +469,13 @@ int ssad_cutpaste_augment(const uint8_t* imgs, const uint8_t* cuts, const ssad_a
  * over the R rows of an L2-normalised bank; the N x R similarity matrix is never written.  Bit-identical to
  * ssad_l2_normalize_rows -> ssad_conv_igemm_fwd (1x1) -> ssad_cosine_knn_mean.  D % 32 == 0. */
 int ssad_cosine_knn_fused(const float* x, const float* bank_normalized, float* out, int64_t N, int D, int R, int k, void* stream);
+/* AnomalyDetector.predict against a large bank (models.py:363-370 of the reference, scored over the whole normal training set):
+ * ssad_cosine_knn_fused split over the bank rows.  Grid (ceil(N / 128), S); split s scores the bank rows [s rp, (s + 1) rp),
+ * rp = 128 ceil(ceil(R / 128) / S), and writes the three smallest distances of each query to part [S][N][3] (caller-owned; INFINITY
+ * where a split has fewer than three rows); a second launch merges the S triples per query in split order.  No float atomics.
+ * Bit-identical to ssad_cosine_knn_fused for every S.  D % 32 == 0, 1 <= S <= 65535. */
+int ssad_cosine_knn_split(const float* x, const float* bank_normalized, float* part, float* out, int64_t N, int D, int R, int k, int S,
+                          void* stream);
 /* Gaussian density estimator (GDE) scorer of CutPaste (csrc/gde.hip; the reference has no such scorer).
  * ssad_gaussian_fit_stats: of the N rows of x [N][D] (each first L2-normalised bit-identically to ssad_l2_normalize_rows when
  * `normalize`), in fp64: mean[D], scatter[D][D] = sum_i (x_i - mean)(x_i - mean)^T and m4[0] = sum_i ||x_i - mean||^4 (the sufficient

@@ -196,6 +196,198 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_fused_kernel(KnnParams p) {
     }
 }
 
+// ================================================ bank-split form ================================================
+// One workgroup per (128-query tile, bank split): the fused kernel's tile body over the bank rows [s rows_per, (s + 1) rows_per)
+// only (rows_per a multiple of BB, so a bank tile sits in one split and every bank row at the same place of its tile as in the fused
+// kernel), the three smallest distances of each query written to part[s][n][0..2] -- INFINITY where the split has fewer than three
+// rows.  A second launch merges the S triples per query.  Meant for big banks and few queries: the fused kernel gives the whole bank
+// to cdiv(N, 128) workgroups, 7 for one image of 841 patches on a 256-CU chip.
+//
+// Operands are staged with buffer loads (gde.hip's mahalanobis_fused_kernel): a scalar base per K-step, one 32-bit offset
+// per staged row, rows past N or R read zeros -- no per-row pointer select in the matrix loop.
+constexpr unsigned OOB = 0x80000000u;   // size given to the buffers: offsets from here on read zeros
+constexpr int SRD3 = 0x00020000;        // raw buffer, 32-bit data format
+
+struct KnnSplitParams {
+    const float* x;       // [N][D] queries (not normalised)
+    const float* bank;    // [R][D] bank rows, L2-normalised
+    float* part;          // [S][N][3] three smallest distances of each query over each split, ascending
+    int64_t N;
+    int D, R, rows_per;
+};
+
+__global__ __launch_bounds__(NT, 2) void cosine_knn_split_kernel(KnnSplitParams p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* nrm_s = lds + 2 * STAGE;             // [BQ]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wb = wave >> 1, wq = wave & 1;    // 64-row bank block / 64-query block of this wave
+    const int64_t m0 = (int64_t)blockIdx.x * BQ;
+    const int sc = tid & 7, sr = tid >> 3;      // staging: 16-byte chunk sc of rows sr + 32 i
+
+    // ---- query norms: cosine_knn_fused_kernel's prologue (l2norm_rows_kernel's order); rows past N get 1 (they read zeros) ----
+    for (int base = wave; base < BQ; base += 32) {
+        float s[8];
+        const float* q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t row = m0 + base + 4 * u;
+            q[u] = row < p.N ? p.x + row * p.D : nullptr;
+            s[u] = 0.f;
+        }
+        for (int k = lane; k < p.D; k += 64) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = q[u] ? q[u][k] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s[u] += v[u] * v[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float t = s[u];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+            if (lane == 0) nrm_s[base + 4 * u] = m0 + base + 4 * u < p.N ? sqrtf(t) : 1.f;
+        }
+    }
+    __syncthreads();
+    float nrm[4];
+    unsigned qoff[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        nrm[i] = nrm_s[sr + 32 * i];
+        qoff[i] = m0 + sr + 32 * i < p.N ? (unsigned)(((sr + 32 * i) * p.D + sc * 4) * 4) : OOB;
+    }
+    const float* xblk = p.x + m0 * p.D;
+
+    float best[TQ][3];
+#pragma unroll
+    for (int j = 0; j < TQ; ++j) best[j][0] = best[j][1] = best[j][2] = INFINITY;
+    const int nks = p.D / BK;
+    const int64_t r_begin = (int64_t)blockIdx.y * p.rows_per;
+    const int r_end = (int)(r_begin + p.rows_per < p.R ? r_begin + p.rows_per : p.R);
+
+    for (int n0 = (int)(r_begin < p.R ? r_begin : p.R); n0 < r_end; n0 += BB) {
+        unsigned boff[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) boff[i] = n0 + sr + 32 * i < p.R ? (unsigned)(((sr + 32 * i) * p.D + sc * 4) * 4) : OOB;
+        const float* bblk = p.bank + (int64_t)n0 * p.D;
+        f32x16 acc[TB][TQ];
+#pragma unroll
+        for (int i = 0; i < TB; ++i)
+#pragma unroll
+            for (int j = 0; j < TQ; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        f32x4 rq[4], rb[4];
+        auto load = [&](int ks) {
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xblk + ks * BK), 0, (int)OOB, SRD3);
+            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(bblk + ks * BK), 0, (int)OOB, SRD3);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                rq[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, qoff[i], 0, 0));
+                rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, boff[i], 0, 0));
+            }
+        };
+        auto store = [&](float* st) {       // normalise while staging: the fused kernel's expression (rows past N: 0 / 1)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rq[i][k] = rq[i][k] / nrm[i];
+                *(f32x4*)(st + (sr + 32 * i) * LDK + sc * 4) = rb[i];
+                *(f32x4*)(st + BB * LDK + (sr + 32 * i) * LDK + sc * 4) = rq[i];
+            }
+        };
+        __syncthreads();
+        load(0);
+        store(lds);
+        __syncthreads();
+        for (int ks = 0; ks < nks; ++ks) {
+            const float* cur = lds + (ks & 1) * STAGE;
+            if (ks + 1 < nks) load(ks + 1);
+            const float* As = cur + (wb * 32 * TB + r) * LDK + h * 4;
+            const float* Bs = cur + BB * LDK + (wq * 32 * TQ + r) * LDK + h * 4;
+#pragma unroll
+            for (int kk = 0; kk < BK / 8; ++kk) {
+                f32x4 a[TB], b[TQ];
+#pragma unroll
+                for (int i = 0; i < TB; ++i) a[i] = *(const f32x4*)(As + i * 32 * LDK + kk * 8);
+#pragma unroll
+                for (int j = 0; j < TQ; ++j) b[j] = *(const f32x4*)(Bs + j * 32 * LDK + kk * 8);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < TB; ++i)
+#pragma unroll
+                        for (int j = 0; j < TQ; ++j) acc[i][j] = mfma32(a[i][e], b[j][e], acc[i][j]);
+            }
+            if (ks + 1 < nks) store(lds + ((ks + 1) & 1) * STAGE);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < TB; ++i) {
+            const int row0 = n0 + (wb * TB + i) * 32 + 4 * h;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const bool ok = row0 + (e & 3) + 8 * (e >> 2) < p.R;
+#pragma unroll
+                for (int j = 0; j < TQ; ++j) {
+                    float d = 1.f - acc[i][j][e];
+                    d = fminf(fmaxf(d, 0.f), 2.f);
+                    keep3(ok ? d : INFINITY, best[j][0], best[j][1], best[j][2]);
+                }
+            }
+        }
+    }
+    // ---- the fused kernel's merge of lane halves and waves, then the triple goes out instead of the mean ----
+    __syncthreads();
+    float* M = lds;                             // [2 wq][TQ][32][3]
+#pragma unroll
+    for (int j = 0; j < TQ; ++j) {
+        const float oa = __shfl_xor(best[j][0], 32), ob = __shfl_xor(best[j][1], 32), oc = __shfl_xor(best[j][2], 32);
+        keep3(oa, best[j][0], best[j][1], best[j][2]);
+        keep3(ob, best[j][0], best[j][1], best[j][2]);
+        keep3(oc, best[j][0], best[j][1], best[j][2]);
+        if (wb == 1 && h == 0) {
+            float* m = M + ((wq * TQ + j) * 32 + r) * 3;
+            m[0] = best[j][0]; m[1] = best[j][1]; m[2] = best[j][2];
+        }
+    }
+    __syncthreads();
+    if (wb == 0 && h == 0) {
+#pragma unroll
+        for (int j = 0; j < TQ; ++j) {
+            const float* m = M + ((wq * TQ + j) * 32 + r) * 3;
+            float a = best[j][0], b = best[j][1], c = best[j][2];
+            keep3(m[0], a, b, c);
+            keep3(m[1], a, b, c);
+            keep3(m[2], a, b, c);
+            const int64_t row = m0 + (wq * TQ + j) * 32 + r;
+            if (row < p.N) {
+                float* o = p.part + ((int64_t)blockIdx.y * p.N + row) * 3;
+                o[0] = a; o[1] = b; o[2] = c;
+            }
+        }
+    }
+}
+
+// out[n] = (a [+ b] [+ c]) / k of the three smallest of the S triples of query n, taken in split order
+__global__ void cosine_knn_merge_kernel(const float* __restrict__ part, float* __restrict__ out, int64_t N, int S, int k) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float a = INFINITY, b = INFINITY, c = INFINITY;
+    for (int s = 0; s < S; ++s) {
+        const float* t = part + ((int64_t)s * N + n) * 3;
+        keep3(t[0], a, b, c);
+        keep3(t[1], a, b, c);
+        keep3(t[2], a, b, c);
+    }
+    float v = a;                                // the k smallest, smallest first: the fused kernel's epilogue
+    if (k > 1) v += b;
+    if (k > 2) v += c;
+    out[n] = v / (float)k;
+}
+
 }  // namespace
 
 // out[n] = mean of the k (1..3) smallest clip(1 - <x_n / ||x_n||, bank_r>, 0, 2) over the R bank rows; bank rows are L2-normalised
@@ -214,6 +406,33 @@ extern "C" int ssad_cosine_knn_fused(const float* x, const float* bank_normalize
     }
     KnnParams p{x, bank_normalized, out, N, D, R, k};
     hipLaunchKernelGGL(cosine_knn_fused_kernel, dim3((unsigned)cdiv64(N, BQ)), dim3(NT), lds_bytes, (hipStream_t)stream, p);
+    SSAD_CHECK_LAUNCH();
+    return 0;
+}
+
+// The bank-split form of ssad_cosine_knn_fused: S workgroups per 128-query tile, split s scoring the bank rows
+// [s rows_per, (s + 1) rows_per) with rows_per = BB * ceil(ceil(R / BB) / S); part [S][N][3] (caller-owned) receives each split's three
+// smallest distances, a second launch merges them per query.  min / max selection and the fused kernel's distance expression and K
+// order: out is bit-identical to ssad_cosine_knn_fused for every S.  No float atomics, two launches on `stream`.
+extern "C" int ssad_cosine_knn_split(const float* x, const float* bank_normalized, float* part, float* out, int64_t N, int D, int R,
+                                     int k, int S, void* stream) {
+    SSAD_CHECK_ARG(x && bank_normalized && part && out && N > 0 && D > 0 && R > 0, "bad argument");
+    SSAD_CHECK_ARG(D % BK == 0 && D <= 65536, "D must be a multiple of 32, at most 65536");
+    SSAD_CHECK_ARG(k >= 1 && k <= 3 && k <= R, "k in 1..3 and <= bank rows");
+    SSAD_CHECK_ARG(S >= 1 && S <= 65535, "S in 1..65535");
+    SSAD_CHECK_ARG(cdiv64(N, BQ) < (int64_t)2147483647, "too many rows for one launch");
+    const int64_t rows_per = cdiv64(cdiv64(R, BB), S) * BB;
+    constexpr int lds_bytes = (2 * STAGE + BQ) * 4;
+    static bool attr_set = false;
+    if (!attr_set) {
+        SSAD_SET_DYN_LDS(cosine_knn_split_kernel, lds_bytes);
+        attr_set = true;
+    }
+    KnnSplitParams p{x, bank_normalized, part, N, D, R, (int)rows_per};
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cosine_knn_split_kernel, dim3((unsigned)cdiv64(N, BQ), (unsigned)S), dim3(NT), lds_bytes, st, p);
+    SSAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(cosine_knn_merge_kernel, dim3((unsigned)cdiv64(N, 256)), dim3(256), 0, st, (const float*)part, out, N, S, k);
     SSAD_CHECK_LAUNCH();
     return 0;
 }

@@ -108,14 +108,16 @@ class GaussianDensityDetector:
                              f"{', 70/30 split' if split else ''}); the image-level bank of tools.inference is one embedding")
         return m
 
-    def fit(self, embeddings: Tensor, split: bool = True) -> None:
-        from .models import split_indices
+    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
+        """groups: image index per row -- the 70/30 split is then drawn over images (models.split_rows)."""
+        from .models import _take, split_rows
         emb = torch.as_tensor(embeddings)
         n = emb.shape[0]
-        self.fit_rows(n, split)
+        if groups is None:
+            self.fit_rows(n, split)
         if split:
-            train_idx, val_idx = split_indices(n, 0.3)
-            train, val = emb[train_idx], emb[val_idx]
+            train_idx, val_idx = split_rows(n, groups, 0.3)
+            train, val = _take(emb, train_idx), _take(emb, val_idx)
         else:
             train, val = emb, emb
         self.fit_bank(train)

@@ -323,6 +323,28 @@ def split_indices(n, test_size=0.3):
     return perm[n_test:], perm[:n_test]
 
 
+def split_rows(n, groups=None, test_size=0.3):
+    """(train, held-out) row indices of the detectors' 70/30 split.  groups=None: split_indices(n) over the rows.  groups [n] (the
+    image index 0..G-1 of every row): the split is drawn over the IMAGES -- split_indices(G), one permutation from the global numpy
+    RNG -- and every row goes with its image, images in the permutation's order, rows ascending within an image.  (A row split would
+    put overlapping patches of one image on both sides and drive the threshold towards 0.)"""
+    if groups is None:
+        return split_indices(n, test_size)
+    g = np.asarray(torch.as_tensor(groups).cpu()).reshape(-1).astype(np.int64)
+    if g.shape[0] != n:
+        raise ValueError(f"groups has {g.shape[0]} entries for {n} rows")
+    order = np.argsort(g, kind="stable")
+    n_groups = int(g.max()) + 1 if n else 0
+    bounds = np.searchsorted(g[order], np.arange(n_groups + 1))
+    tr, va = split_indices(n_groups, test_size)
+    take = lambda ids: (np.concatenate([order[bounds[i]:bounds[i + 1]] for i in ids]) if len(ids) else np.zeros(0, np.int64))
+    return take(tr), take(va)
+
+
+def _take(t, idx):
+    return t[torch.as_tensor(idx, dtype=torch.int64, device=t.device)]
+
+
 class AnomalyDetector:
     """src/self_supervised/models.py:345-370: cosine 3-NN distance to a bank of normal embeddings.
 
@@ -346,12 +368,13 @@ class AnomalyDetector:
             t = t.cuda()
         return t.contiguous()
 
-    def fit(self, embeddings: Tensor, split: bool = True) -> None:
+    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
+        """groups: image index per row -- the 70/30 split is then drawn over images (split_rows)."""
         emb = torch.as_tensor(embeddings)
         n = emb.shape[0]
         if split:
-            train_idx, val_idx = split_indices(n, 0.3)
-            train, val = emb[train_idx], emb[val_idx]
+            train_idx, val_idx = split_rows(n, groups, 0.3)
+            train, val = _take(emb, train_idx), _take(emb, val_idx)
         else:
             train, val = emb, emb
         self.k = 3

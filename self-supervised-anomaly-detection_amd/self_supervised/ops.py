@@ -658,10 +658,45 @@ def cosine_knn_mean(sim, k=3):
     return out
 
 
-def cosine_knn_fused(x, bank_n, k=3):
-    """x [N][D] (not normalised), bank_n [R][D] L2-normalised -> [N] mean of the k smallest cosine distances, one kernel."""
+KNN_SPLIT_TARGET_WG = 3072  # workgroups a split launch aims at: 12 per CU of an MI355X (256 CUs), 6 rounds of the 2 resident
+KNN_SPLIT_MIN_ROWS = 4096   # bank rows a split keeps at the least
+
+
+def knn_splits(n, r):
+    """Bank splits S of cosine_knn_fused for n queries against r bank rows: 1 -- the one-launch kernel -- when the 128-query tiles
+    alone reach KNN_SPLIT_TARGET_WG workgroups or the bank has fewer than 2 x KNN_SPLIT_MIN_ROWS rows; else enough splits to reach
+    that many workgroups, each split keeping at least KNN_SPLIT_MIN_ROWS rows.  Tuned with tools/knn_split_probe.py: a
+    launch of few workgroups leaves CUs idle, and one of about 2 per CU leaves a half-empty last round.  The 588-row bank of the
+    reference path and the million-query WideResNet-50 scales stay at 1.  SSAD_KNN_SPLIT=0 forces 1 (A/B runs)."""
+    if os.environ.get("SSAD_KNN_SPLIT", "1") == "0":
+        return 1
+    tiles = -(-int(n) // 128)
+    if tiles >= KNN_SPLIT_TARGET_WG:
+        return 1
+    return max(1, min(-(-KNN_SPLIT_TARGET_WG // tiles), int(r) // KNN_SPLIT_MIN_ROWS))
+
+
+def cosine_knn_split(x, bank_n, k=3, splits=1):
+    """cosine_knn_fused with the bank split S = `splits` ways (csrc/knn.hip ssad_cosine_knn_split): two launches, a [S][N][3]
+    workspace; bit-identical to the one-launch kernel for every S."""
     n, d = x.shape
     r = bank_n.shape[0]
+    out = _new((n,), x)
+    part = _new((int(splits), n, 3), x)
+    _run("knn_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + n + 6 * part.numel()),
+         lambda: _hip.lib().ssad_cosine_knn_split(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(part), _hip.ptr(out), n, d, r, k,
+                                                  int(splits), _hip.stream()))
+    return out
+
+
+def cosine_knn_fused(x, bank_n, k=3):
+    """x [N][D] (not normalised), bank_n [R][D] L2-normalised -> [N] mean of the k smallest cosine distances, one kernel; split over
+    the bank rows (cosine_knn_split, same bits) when few queries meet a large bank (knn_splits)."""
+    n, d = x.shape
+    r = bank_n.shape[0]
+    s = knn_splits(n, r)
+    if s > 1:
+        return cosine_knn_split(x, bank_n, k, s)
     out = _new((n,), x)
     _run("knn_fused", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + n),
          lambda: _hip.lib().ssad_cosine_knn_fused(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(out), n, d, r, k, _hip.stream()))

@@ -362,12 +362,53 @@ def _check_detector(detector):
     return detector
 
 
+BANKS = ('reference', 'train')
+
+
+def _check_bank(bank, mvtec_inference=True):
+    if bank not in BANKS:
+        raise ValueError(f"bank must be one of {BANKS}, got {bank!r}")
+    if bank == 'train' and not mvtec_inference:
+        raise ValueError("bank='train' needs mvtec_inference=True: the pretext datamodule has no plain set of normal images")
+    return bank
+
+
+def _embed_files(model, tester, dataset, files):
+    """Embeddings of `files` (per image: [patches][D], in order) through ``Trainer.predict`` over an UNSHUFFLED loader of batch size 1
+    with the test dataset's transform -- the route for training images when the streamed predict is off."""
+    from .datasets import MVTecDataset
+    if not files:
+        return []
+    ds = MVTecDataset(dataset.dataset_dir, list(files), imsize=dataset.imsize, transform=dataset.transform)
+    dm = MVTecDatamodule(dataset.dataset_dir, batch_size=1)
+    preds = tester.predict(model, dataloaders=dm._loader(ds, False))
+    return [torch.as_tensor(c.embedding_vectors).detach().cpu() for c in preds]
+
+
+def _train_bank_rows(per_image, n_total, device):
+    """This rank's per-image training embeddings (images rank, rank + world, ...) -> (rows [n_total * P][D] of every training image in
+    file order, groups [rows]: the image index of each row).  One exchange under torch.distributed (gather_in_order); with one rank
+    the rows stay where they are."""
+    rank, world = world_info()
+    if world > 1:
+        per_image = gather_in_order([t.cpu() for t in per_image], n_total)
+    if not per_image:
+        raise ValueError("bank='train': the category has no training images (train/good is empty)")
+    rows = torch.cat([t.to(device) for t in per_image]) if world > 1 or len(per_image) > 1 else per_image[0]
+    groups = torch.repeat_interleave(torch.arange(len(per_image)), torch.tensor([int(t.shape[0]) for t in per_image]))
+    return rows.contiguous(), groups
+
+
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
-              patch_localization: bool = False, detector: str = 'knn') -> ModelOutputsContainer:
+              patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference') -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
-    estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows, so
-    patch level only -- the image-level bank is one embedding, quirk Q3)."""
+    estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
+    `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
+    (quirks Q3 / Q4), so image-level 'gde' raises.  'train' = every image of train/good in file order (one row per image at image
+    level, its patches at patch level), the 70/30 split drawn over images; MVTec data only."""
     scorer = _check_detector(detector)
+    _check_bank(bank, mvtec_inference)
+    whole = bank == 'train'
     del TIMELINE[:]
     print('>>> initializing inference')
     # MVTec test data: file lists and decode threads start BEFORE the checkpoint is read, so that the first group of images is
@@ -380,6 +421,14 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         datamodule.setup('predict')
         if _fast_mvtec_ok(datamodule.test_dataset):
             mine = list(range(rank, len(datamodule.test_dataset), world)) if world > 1 else list(range(len(datamodule.test_dataset)))
+        if whole:
+            # bank='train': every training image, round-robin over the ranks, embedded in the same stream as the test images (in
+            # front of them); no generator draws -- no image is chosen
+            train_files = list(datamodule.train_images_filenames)
+            my_train = train_files[rank::world]
+            if _fast_mvtec_ok(datamodule.test_dataset):     # (a rank without test images embeds its share through Trainer.predict)
+                prefetch = _MVTecPrefetch(datamodule.test_dataset, mine, extra_files=my_train if mine else ())
+        elif _fast_mvtec_ok(datamodule.test_dataset):
             # Which training image becomes the normality bank (tools.py:374-381: element [0] of a prediction over the SHUFFLED training
             # loader) is decided by two draws from torch's global generator -- the test loader's base seed, then the training loader's
             # base seed and its sampler's seed.  Nothing between here and there draws from it (the model is built on the meta device, the
@@ -429,7 +478,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         # size 1 (same values; _predict_mvtec_streamed).  The DataLoader iterator the reference creates here draws its base
         # seed from torch's global generator: the draw is kept, so that what follows (the shuffled loader of the normality
         # image) sees the same generator state
-        if bank_file is None:
+        if bank_file is None and not whole:
             torch.empty((), dtype=torch.int64).random_()
         model.to(tester.device).eval()
         _mark("model-on-device")
@@ -442,12 +491,26 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         output.from_list(predictions)
         n_pred = len(predictions)
     print('>>> anomaly detection phase')
+    groups = None
     kind = GaussianDensityDetector if scorer == 'gde' else AnomalyDetector
     if patch_localization:
         detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches)
     else:
         detector = kind()
-    if model.memory_bank.shape[0] > 1000:            # quirk Q3: the bank is capped at 1000 rows, so this never holds
+    if whole:
+        # the training images' embeddings: from the stream (in front of the test images) or, with the streamed predict off or no test
+        # images on this rank, from Trainer.predict over an unshuffled loader -- the same rows either way
+        extra = getattr(output, "extra_embeddings", None)
+        if extra is not None:
+            p_img = extra.shape[0] // len(my_train)
+            mine_train = [extra[j * p_img:(j + 1) * p_img] for j in range(len(my_train))]
+            del output.extra_embeddings
+        else:
+            mine_train = _embed_files(model, tester, datamodule.test_dataset, my_train)
+        print(f' fitting on the whole training set ({len(train_files)} images)')
+        normality, groups = _train_bank_rows(mine_train, len(train_files), tester.device)
+        _mark("train-bank")
+    elif model.memory_bank.shape[0] > 1000:            # quirk Q3: the bank is capped at 1000 rows, so this never holds
         normality = model.memory_bank
     elif bank_file is not None and getattr(output, "extra_embeddings", None) is not None:
         print(' not enough data in memory bank, sampling new data trom train set')
@@ -481,13 +544,18 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         output_normality.to_cpu()
         normality = output_normality.embedding_vectors
     output.to_cpu()
-    if scorer == 'gde':
+    if scorer == 'gde' and groups is not None:
+        # on every rank, before anybody waits for a broadcast: the rows of the images the 70/30 split keeps
+        n_img = len(train_files)
+        GaussianDensityDetector.fit_rows((n_img - int(np.ceil(0.3 * n_img))) * (int(normality.shape[0]) // max(1, n_img)), split=False)
+    elif scorer == 'gde':
         GaussianDensityDetector.fit_rows(int(normality.shape[0]))      # on every rank, before anybody waits for a broadcast
+    fit_kw = {} if groups is None else {"groups": groups}      # (the default bank: the reference's fit call, unchanged)
     if world > 1:
         # one bank for everybody: rank 0 draws the 70/30 split and fits, the others receive (bank, threshold) -- (state, threshold)
         # of the Gaussian for 'gde'
         if rank == 0:
-            detector.fit(normality)
+            detector.fit(normality, **fit_kw)
             payload = (detector.state() if scorer == 'gde' else detector.bank.cpu(), detector.threshold)
         state = broadcast_bank(payload if rank == 0 else None)
         if rank != 0:
@@ -498,7 +566,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
             else:
                 detector.bank, detector.threshold = AnomalyDetector._dev(state[0]), state[1]
     else:
-        detector.fit(normality)
+        detector.fit(normality, **fit_kw)
     _mark("bank-fitted")
     print(' computing anomaly scores')
     output.anomaly_maps = detector.predict(emb_dev if emb_dev is not None else output.embedding_vectors).cpu()
@@ -547,13 +615,14 @@ def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64)
 def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = (256, 256), patch_localization: bool = True,
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
-          detector: str = 'knn'):
+          detector: str = 'knn', bank: str = 'reference'):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
-    category.  Returns the pandas DataFrame (identical on every rank).  `detector` as in `inference` ('knn' or 'gde')."""
+    category.  Returns the pandas DataFrame (identical on every rank).  `detector` and `bank` as in `inference`."""
     _check_detector(detector)
+    _check_bank(bank)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows = {}
@@ -566,7 +635,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
                          batch_size=batch_size, projection_training_params=projection_training_params,
                          fine_tune_params=fine_tune_params, trainer_kwargs=trainer_kwargs)
             out = inference(sub_out + 'best_model.ckpt', data, subject, mvtec_inference=True,
-                            patch_localization=patch_localization, detector=detector)
+                            patch_localization=patch_localization, detector=detector, bank=bank)
         if patch_localization:
             out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False)      # stays on the device: the Evaluator's GPU metrics
         ev = Evaluator(evaluation_metrics=[m for m in metrics if (m != 'f1-score') == patch_localization or m == 'auroc'])
