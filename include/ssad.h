@@ -227,6 +227,21 @@ int ssad_wgrad_reduce(const float* slab, float* dw, int splits, int Cout, int Kp
  * Same order of additions per output as ssad_wgrad_reduce: bit-identical.  OHWI outputs, no accumulation; Kreal % 4 == 0, Kpad % 4 == 0,
  * 16-byte aligned pointers.  Same autograd nodes as ssad_conv_wgrad (Conv2d weight gradients under trainer.fit, models.py:256-277). */
 int ssad_wgrad_reduce_batch(const int64_t* desc, int n, void* stream);
+/* The instantiation a weight-gradient launch of a given path runs -- the launchers take their template arguments from this same
+ * function.  Host-only (no GPU needed); test aid (tests/test_wgrad_path_table.py pins the selection), no reference counterpart.
+ *   SSAD_WGRAD_GENERIC  ssad_conv_wgrad and its 16-bit / split-bf16 forms: the channel tile BT, 64 or 128
+ *   SSAD_WGRAD_HALO     ssad_conv_wgrad3x3_halo (stride 1) / ssad_conv_wgrad3x3s2_halo (stride 2)   the output-pixel tile,
+ *   SSAD_WGRAD_HALO16   ssad_conv_wgrad3x3_halo16(_h) (stride 1)                                     TH * 100 + TW
+ *   SSAD_WGRAD_G16      ssad_conv_wgrad3x3_g16_h (stride 1 or 2)                                     (416 = 4 x 16, ...)
+ *   SSAD_WGRAD_STEM     ssad_stem_wgrad (dz_half 0) / ssad_stem_wgrad_h (dz_half 1): 0 fp32 dz, 1 half dz on the fp32 MFMAs,
+ *                       2 fp16 operands
+ * Wo: width of dz (the conv's OUTPUT).  -1 for an unknown path. */
+#define SSAD_WGRAD_GENERIC 0
+#define SSAD_WGRAD_HALO 1
+#define SSAD_WGRAD_HALO16 2
+#define SSAD_WGRAD_G16 3
+#define SSAD_WGRAD_STEM 4
+int ssad_wgrad_variant_id(int path, int Wo, int Cin, int Cout, int stride, int dz_half);
 /* bf16-operand forms of the three MFMA entry points above (fp32 tensors in HBM; operands rounded to bf16 while staging,
  * fp32 accumulate; v_mfma_f32_32x32x16_bf16).  This is what torch.autocast does to the same Conv2d / Linear call sites
  * under the reference's pl.Trainer(precision=16) (src/self_supervised/tools.py:263, :296). */
@@ -309,6 +324,7 @@ int ssad_stem_im2col(const float* img, float* col, int64_t B, int H, int W, int 
  * 64x64 go through the same nearest resize).  dw receives 64*7*7*3 floats, OHWI or (to_oihw) OIHW, optionally
  * accumulated.  workspace: ssad_stem_wgrad_workspace(B, H, W) floats (per-workgroup slabs, summed in a fixed order). */
 int64_t ssad_stem_wgrad_workspace(int B, int H, int W);
+int ssad_stem_wgrad_splits(int B, int H, int W);     /* slabs in that workspace (= the reduction's split count); host-only */
 int ssad_stem_wgrad(const float* img, const float* dz, float* dw, int B, int H, int W, int64_t dz_elems, int to_oihw,
                     int accumulate, float* workspace, void* stream);
 int ssad_pack_stem_weight_2d(const float* w_oihw, float* out, void* stream);

@@ -53,6 +53,14 @@ int ssad_linear_small_launch(const float* a, const float* b, float* y, const flo
                              const float* residual, int relu, int M, int K, int N, double* stats, int* stat_rows, void* stream,
                              int round = 0);      // round: operands rounded to bf16 (1) / fp16 (2) as they are loaded
 
+// Instantiation choices of the weight-gradient launchers, gathered by ssad_wgrad_variant_id (wgrad.hip): the output-pixel tile
+// TH * 100 + TW of wgrad_halo.hip / wgrad_halo16.hip / wgrad16.hip (Wo: width of dz), stem_wgrad.hip's kernel for dz stored as
+// floats (dz_half 0) or halves (1)
+int wgrad_halo_tile(int Wo, int stride);
+int wgrad_halo16_tile(int Wo);
+int wgrad_g16_tile(int Wo, int stride);
+int stem_wgrad_kernel_id(int dz_half);
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Storage type of an activation tensor: float, or _Float16 for the precision-16 step whose tensors live in HBM as halves (what

@@ -273,11 +273,22 @@ int stem_wgrad_blocks(int64_t total_tiles) {
 
 }  // namespace
 
-extern "C" int64_t ssad_stem_wgrad_workspace(int B, int H, int W) {
+extern "C" int ssad_stem_wgrad_splits(int B, int H, int W) {
     const int Hv = (H < 64 || W < 64) ? 64 : H, Wv = (H < 64 || W < 64) ? 64 : W;
     const int Ho = (Hv - 1) / 2 + 1, Wo = (Wv - 1) / 2 + 1;
     const int64_t tiles = (int64_t)B * ((Ho + TH - 1) / TH) * ((Wo + TW - 1) / TW);
-    return (int64_t)stem_wgrad_blocks(tiles) * 64 * KPAD;
+    return stem_wgrad_blocks(tiles);
+}
+
+extern "C" int64_t ssad_stem_wgrad_workspace(int B, int H, int W) {
+    return (int64_t)ssad_stem_wgrad_splits(B, H, W) * 64 * KPAD;
+}
+
+// 0: stem_wgrad_kernel<float>; dz stored as halves: 2 = stem_wgrad16_kernel (fp16 operands, image rounded), or 1 =
+// stem_wgrad_kernel<hf> (exact products of the stored values on the fp32 MFMAs) under SSAD_STEM_WGRAD16=0
+int stem_wgrad_kernel_id(int dz_half) {
+    static const int f16 = getenv("SSAD_STEM_WGRAD16") ? atoi(getenv("SSAD_STEM_WGRAD16")) : 1;
+    return !dz_half ? 0 : f16 ? 2 : 1;
 }
 
 static int stem_wgrad_impl(const float* img, const void* dz, int dz_half, float* dw, int B, int H, int W, int64_t dz_elems, int to_oihw,
@@ -298,9 +309,10 @@ static int stem_wgrad_impl(const float* img, const void* dz, int dz_half, float*
     // nearest resize was read out of bounds here): the caller states what its buffer holds
     SSAD_CHECK_ARG(dz_elems == (int64_t)B * p.Ho * p.Wo * 64, "dz does not hold B x Ho x Wo x 64 elements for these images");
     const int nblk = stem_wgrad_blocks(p.total_tiles);
-    // dz_half: 1 = halves read into the fp32-MFMA kernel (exact products of the stored values); 2 = fp16 operands (image rounded)
-    if (dz_half == 2) hipLaunchKernelGGL(stem_wgrad16_kernel, dim3(nblk), dim3(256), (DY_FLOATS + IN_FLOATS) * 4, (hipStream_t)stream, p);
-    else if (dz_half) hipLaunchKernelGGL(stem_wgrad_kernel<hf>, dim3(nblk), dim3(256), (DY_FLOATS + IN_FLOATS) * 4, (hipStream_t)stream, p);
+    // kernel: 1 = halves read into the fp32-MFMA kernel (exact products of the stored values); 2 = fp16 operands (image rounded)
+    const int kernel = stem_wgrad_kernel_id(dz_half);
+    if (kernel == 2) hipLaunchKernelGGL(stem_wgrad16_kernel, dim3(nblk), dim3(256), (DY_FLOATS + IN_FLOATS) * 4, (hipStream_t)stream, p);
+    else if (kernel == 1) hipLaunchKernelGGL(stem_wgrad_kernel<hf>, dim3(nblk), dim3(256), (DY_FLOATS + IN_FLOATS) * 4, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(stem_wgrad_kernel<float>, dim3(nblk), dim3(256), (DY_FLOATS + IN_FLOATS) * 4, (hipStream_t)stream, p);
     SSAD_CHECK_LAUNCH();
     return ssad_wgrad_reduce(workspace, dw, nblk, 64, KPAD, 7, 7, 3, to_oihw, accumulate, stream);
@@ -314,6 +326,5 @@ extern "C" int ssad_stem_wgrad(const float* img, const float* dz, float* dw, int
 // dz stored as halves (precision-16 step); products and sums in fp32 as above
 extern "C" int ssad_stem_wgrad_h(const float* img, const void* dz, float* dw, int B, int H, int W, int64_t dz_elems, int to_oihw,
                                  int accumulate, float* workspace, void* stream) {
-    static const int f16 = getenv("SSAD_STEM_WGRAD16") ? atoi(getenv("SSAD_STEM_WGRAD16")) : 1;
-    return stem_wgrad_impl(img, dz, f16 ? 2 : 1, dw, B, H, W, dz_elems, to_oihw, accumulate, workspace, stream);
+    return stem_wgrad_impl(img, dz, 1, dw, B, H, W, dz_elems, to_oihw, accumulate, workspace, stream);
 }

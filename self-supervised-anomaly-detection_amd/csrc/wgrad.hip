@@ -12,6 +12,7 @@
 // and one pixel range; partial tiles go to slab[split] and ssad_wgrad_reduce sums the splits in a fixed order
 // (deterministic, no float atomics), writing OIHW (checkpoint layout) or OHWI.
 #include "common.h"
+#include "ssad.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -515,8 +516,11 @@ static int resident_per_cu(int BT, bool bf16) {
     return BT == 64 ? 4 : 2;                // 8-wave workgroups: 32 waves per CU / 64 KB LDS
 }
 
+// Channel tile of the split kernels: a 128-wide tile would be half empty when either side has <= 64 channels
+static int wgrad_bt(int Cin, int Cout) { return (Cin <= 64 || Cout <= 64) ? 64 : 128; }
+
 static int choose_splits(int64_t M, int Cin, int Cout, int KH, int KW, bool bf16) {
-    const int BT = (Cin <= 64 || Cout <= 64) ? 64 : 128;   // a 128-wide tile would be half empty
+    const int BT = wgrad_bt(Cin, Cout);
     const int64_t tiles = (int64_t)KH * KW * ((Cout + BT - 1) / BT) * ((Cin + BT - 1) / BT);
     static const int target = getenv("SSAD_WGRAD_BLOCKS") ? atoi(getenv("SSAD_WGRAD_BLOCKS")) : 0;
     const int64_t max_splits = (M + 255) / 256;            // at least 256 pixels per workgroup
@@ -555,6 +559,19 @@ extern "C" int ssad_wgrad_splits_bf16(int64_t M, int Cin, int Cout, int KH, int 
     return choose_splits(M, Cin, Cout, KH, KW, true);
 }
 
+// The instantiation a weight-gradient launch runs; every launcher below and in wgrad_halo / wgrad_halo16 / wgrad16 / stem_wgrad
+// takes its template arguments from here, so the reporter and the launch cannot disagree (include/ssad.h).
+extern "C" int ssad_wgrad_variant_id(int path, int Wo, int Cin, int Cout, int stride, int dz_half) {
+    switch (path) {
+    case SSAD_WGRAD_GENERIC: return wgrad_bt(Cin, Cout);
+    case SSAD_WGRAD_HALO: return wgrad_halo_tile(Wo, stride);
+    case SSAD_WGRAD_HALO16: return wgrad_halo16_tile(Wo);
+    case SSAD_WGRAD_G16: return wgrad_g16_tile(Wo, stride);
+    case SSAD_WGRAD_STEM: return stem_wgrad_kernel_id(dz_half);
+    default: return -1;
+    }
+}
+
 static int wgrad_impl(const float* dy, const float* x, float* slab, int splits, int64_t N, int H, int W, int Cin,
                                int Cout, int KH, int KW, int stride, int pad, int64_t dy_elems, void* stream, int bf16, int half_in = 0) {
     SSAD_CHECK_ARG(!half_in || bf16 == 2, "half tensors go with fp16 operands");
@@ -573,7 +590,7 @@ static int wgrad_impl(const float* dy, const float* x, float* slab, int splits, 
     SSAD_CHECK_ARG(dy_elems == p.M * Cout, "dy does not hold N x Ho x Wo x Cout elements for this x / filter geometry");
     int64_t chunk = (p.M + splits - 1) / splits;
     p.chunk = (chunk + PK - 1) / PK * PK;
-    const int BT = (Cin <= 64 || Cout <= 64) ? 64 : 128;   // a 128-wide tile would be half empty
+    const int BT = ssad_wgrad_variant_id(SSAD_WGRAD_GENERIC, 0, Cin, Cout, 0, 0);
     p.co_tiles = (Cout + BT - 1) / BT;
     p.ci_tiles = (Cin + BT - 1) / BT;
     p.splits = splits;

@@ -178,10 +178,21 @@ struct G16Geo {
     int64_t ntiles, chunk;
 };
 
+}  // namespace
+
+// Output-pixel tile (TH * 100 + TW): 64 pixels at stride 1, 32 at stride 2
+int wgrad_g16_tile(int Wo, int S) {
+    const int TW = Wo > 8 ? 16 : 8;
+    return (S == 1 ? 64 : 32) / TW * 100 + TW;
+}
+
+namespace {
+
 static G16Geo g16_geometry(int64_t N, int Ho, int Wo, int Cin, int Cout, int S) {
     G16Geo g;
-    g.TW = Wo > 8 ? 16 : 8;
-    g.TH = (S == 1 ? 64 : 32) / g.TW;
+    const int tile = wgrad_g16_tile(Wo, S);
+    g.TW = tile % 100;
+    g.TH = tile / 100;
     g.tiles_y = (Ho + g.TH - 1) / g.TH;
     g.tiles_x = (Wo + g.TW - 1) / g.TW;
     g.ntiles = N * g.tiles_y * g.tiles_x;

@@ -205,6 +205,14 @@ static int halo_splits(int64_t ntiles, int npairs) {
 
 }  // namespace
 
+// Output-pixel tile (TH * 100 + TW) of a launch over dz of width Wo: 64-pixel tiles (144 accumulator + 44 staging registers fit);
+// stride 2 takes 4 x 8 so that two workgroups fit a CU unless SSAD_WGRAD_HALO_S2_TILE asks for the 64-pixel forms
+int wgrad_halo_tile(int Wo, int stride) {
+    static const int s2_tile = getenv("SSAD_WGRAD_HALO_S2_TILE") ? atoi(getenv("SSAD_WGRAD_HALO_S2_TILE")) : 32;
+    if (stride == 2 && s2_tile == 32) return 408;
+    return Wo > 8 ? 416 : 808;
+}
+
 // 1 when ssad_conv_wgrad3x3_halo handles the layer.
 extern "C" int ssad_wgrad3x3_halo_ok(int Cin, int Cout, int KH, int KW, int stride, int pad) {
     static const int s2 = getenv("SSAD_WGRAD_HALO_S2") ? atoi(getenv("SSAD_WGRAD_HALO_S2")) : 1;
@@ -225,9 +233,9 @@ static int halo_launch(const float* dz, const float* x, float* slab, int splits,
     SSAD_CHECK_ARG(Cin % 64 == 0 && Cout % 64 == 0, "channel counts must be multiples of 64");
     SSAD_CHECK_ARG((int64_t)Hx * Wx * Cin < (int64_t)1 << 28 && (int64_t)H * W * Cout < (int64_t)1 << 28 &&
                    N * (int64_t)((H + 3) / 4) * ((W + 7) / 8) < (int64_t)1 << 31, "an image must stay below 1 GB (32-bit buffer offsets), tile numbers int");
-    static const int s2_tile = getenv("SSAD_WGRAD_HALO_S2_TILE") ? atoi(getenv("SSAD_WGRAD_HALO_S2_TILE")) : 32;
-    const bool half = S == 2 && s2_tile == 32;             // stride 2: 4 x 8 output pixels, so that two workgroups fit a CU
-    const int TW = half ? 8 : W > 8 ? 16 : 8, TH = half ? 4 : W > 8 ? 4 : 8;     // 64-pixel tiles: 144 accumulator + 44 staging registers fit
+    const int tile = wgrad_halo_tile(W, S);
+    const bool half = S == 2 && tile == 408;              // stride 2: 4 x 8 output pixels, so that two workgroups fit a CU
+    const int TW = tile % 100, TH = tile / 100;
     WgHaloParams p;
     p.dz = dz; p.x = x; p.slab = slab; p.N = (int)N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Hx = Hx; p.Wx = Wx;
     p.tiles_y = (H + TH - 1) / TH; p.tiles_x = (W + TW - 1) / TW;

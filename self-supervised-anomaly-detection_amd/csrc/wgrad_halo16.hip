@@ -231,6 +231,9 @@ static int halo16_splits(int64_t ntiles, int npairs) {
 
 }  // namespace
 
+// Output-pixel tile (TH * 100 + TW) over a map of width W
+int wgrad_halo16_tile(int W) { return W > 8 ? 416 : 808; }
+
 // 1 when ssad_conv_wgrad3x3_halo16 handles the layer (3 x 3, stride 1, pad 1, channel counts multiples of 64).
 extern "C" int ssad_wgrad3x3_halo16_ok(int Cin, int Cout, int KH, int KW, int stride, int pad) {
     static const int on = getenv("SSAD_WGRAD_HALO16") ? atoi(getenv("SSAD_WGRAD_HALO16")) : 1;
@@ -238,7 +241,7 @@ extern "C" int ssad_wgrad3x3_halo16_ok(int Cin, int Cout, int KH, int KW, int st
 }
 
 extern "C" int ssad_wgrad3x3_halo16_splits(int64_t N, int H, int W, int Cin, int Cout) {
-    const int TW = W > 8 ? 16 : 8, TH = W > 8 ? 4 : 8;
+    const int tile = wgrad_halo16_tile(W), TW = tile % 100, TH = tile / 100;
     const int64_t ntiles = N * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
     return halo16_splits(ntiles, (Cin / 64) * (Cout / 64));
 }
@@ -253,7 +256,7 @@ static int wgrad3x3_halo16_impl(const void* dz, const void* x, int half_in, floa
     SSAD_CHECK_ARG(Cin % 64 == 0 && Cout % 64 == 0, "channel counts must be multiples of 64");
     SSAD_CHECK_ARG((int64_t)H * W * Cin < (int64_t)1 << 32 && (int64_t)H * W * Cout < (int64_t)1 << 32 &&
                    N * (int64_t)((H + 3) / 4) * ((W + 7) / 8) < (int64_t)1 << 31, "offsets inside an image are 32-bit, tile numbers int");
-    const int TW = W > 8 ? 16 : 8, TH = W > 8 ? 4 : 8;
+    const int tile = wgrad_halo16_tile(W), TW = tile % 100, TH = tile / 100;
     WgH16Params p;
     p.dz = dz; p.x = x; p.slab = slab; p.N = (int)N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
     p.tiles_y = (H + TH - 1) / TH; p.tiles_x = (W + TW - 1) / TW;

@@ -108,6 +108,7 @@ SIGNATURES = {
     "ssad_conv_wgrad_x3": [_c_fp, _c_fp, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_l, _c_fp],
     "ssad_conv_wgrad_x6": [_c_fp, _c_fp, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_l, _c_fp],
     "ssad_wgrad_reduce_batch": [ctypes.POINTER(ctypes.c_int64), _c_i, _c_fp],
+    "ssad_wgrad_variant_id": [_c_i, _c_i, _c_i, _c_i, _c_i, _c_i],
     "ssad_wgrad_reduce": [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_stem_im2col": [_c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_pack_stem_weight_2d": [_c_fp, _c_fp, _c_fp],
@@ -120,6 +121,7 @@ SIGNATURES = {
                               _c_l, _c_fp, _c_fp],
     "ssad_gradcam_map": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     "ssad_stem_wgrad_workspace": [_c_i, _c_i, _c_i],
+    "ssad_stem_wgrad_splits": [_c_i, _c_i, _c_i],
     "ssad_stem_wgrad": [_c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp],
     "ssad_conv_stats_workspace": [_c_l, _c_i, _c_i, _c_i],
     "ssad_conv_igemm_fwd_stats": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,

@@ -856,93 +856,130 @@ def conv_dgrad(dy, w_flipT, x_shape, stride, pad, residual=None, bf16=False, res
     return dx
 
 
+# Weight-gradient paths (ssad_wgrad_variant_id, include/ssad.h): the instantiation a path's launcher runs
+WGRAD_GENERIC, WGRAD_HALO, WGRAD_HALO16, WGRAD_G16, WGRAD_STEM = range(5)
+_WGRAD_TILES = {416: "4x16", 808: "8x8", 408: "4x8", 216: "2x16"}       # TH * 100 + TW of the output-pixel tile
+_WGRAD_MODES = {0: "f32", 1: "bf16", 2: "f16", 3: "x3", 6: "x6"}
+STEM_WGRAD_KERNELS = ("float", "hf", "f16")     # stem_wgrad_kernel<float>, stem_wgrad_kernel<hf>, stem_wgrad16_kernel
+
+
+def wgrad_path(dy_shape, x_shape, kh, kw, stride, pad, bf16=False, half=False, force_x6=False, kreal=None):
+    """(path, instantiation, splits) of the launch conv_wgrad makes for dy NHWC dy_shape, x NHWC x_shape (half: both stored as
+    halves) -- conv_wgrad takes its branch from here.  Paths: linear_small (instantiation = operand rounding f32 / bf16 / f16, no slab:
+    splits 0); halo_s1 / halo_s2 (fp32 tensors), halo16_bf16 / halo16_f16 (fp32 tensors, 16-bit operands), halo16_h, g16_s1 / g16_s2
+    (half tensors): the output-pixel tile TH x TW; generic_f32 / _bf16 / _f16 / _x3 / _x6 / _f16_h: the channel tile BT64 / BT128.
+    splits = the slab count the reduction sums.  Host-only (no GPU needed)."""
+    lib = _hip.lib()
+    n, h, w, cin = (int(v) for v in x_shape)
+    ho, wo, cout = int(dy_shape[1]), int(dy_shape[2]), int(dy_shape[-1])
+    m = n * ho * wo
+    mode = 0 if int(bf16) == 6 and not force_x6 else int(bf16)     # (bf16x6 training: see the generic branch of conv_wgrad)
+    tile = lambda path: _WGRAD_TILES[lib.ssad_wgrad_variant_id(path, wo, cin, cout, stride, 0)]
+    bt = lambda: "BT%d" % lib.ssad_wgrad_variant_id(WGRAD_GENERIC, wo, cin, cout, stride, 0)
+    if half:
+        assert mode == 2 and kreal is None, "half tensors go with fp16 operands"
+        if lib.ssad_wgrad3x3_g16_ok(cin, cout, kh, kw, stride, pad):
+            return "g16_s%d" % stride, tile(WGRAD_G16), lib.ssad_wgrad3x3_g16_splits(n, ho, wo, cin, cout, stride)
+        if lib.ssad_wgrad3x3_halo16_ok(cin, cout, kh, kw, stride, pad):
+            return "halo16_h", tile(WGRAD_HALO16), lib.ssad_wgrad3x3_halo16_splits(n, h, w, cin, cout)
+        return "generic_f16_h", bt(), lib.ssad_wgrad_splits_bf16(m, cin, cout, kh, kw)
+    if mode in (0, 1, 2) and kreal is None and kh == kw == h == w == 1 and m <= lib.ssad_linear_small_max_rows():
+        return "linear_small", _WGRAD_MODES[mode], 0
+    if mode == 0 and kreal is None and os.environ.get("SSAD_WGRAD_HALO", "1") != "0":
+        halo = lib.ssad_wgrad3x3_halo_ok(cin, cout, kh, kw, stride, pad)
+        if halo:
+            return "halo_s%d" % halo, tile(WGRAD_HALO), lib.ssad_wgrad3x3_halo_splits(n, ho, wo, cin, cout)
+    if mode in (1, 2) and kreal is None and lib.ssad_wgrad3x3_halo16_ok(cin, cout, kh, kw, stride, pad):
+        return "halo16_" + _WGRAD_MODES[mode], tile(WGRAD_HALO16), lib.ssad_wgrad3x3_halo16_splits(n, h, w, cin, cout)
+    splits = (lib.ssad_wgrad_splits_bf16 if mode else lib.ssad_wgrad_splits)(m, cin, cout, kh, kw)
+    return "generic_" + _WGRAD_MODES[mode], bt(), splits
+
+
 def conv_wgrad(dy, x, dw_out, kh, kw, stride, pad, kreal=None, to_oihw=False, accumulate=False, bf16=False, force_x6=False):
     """dy NHWC [N][Ho][Wo][Cout], x NHWC [N][H][W][Cin] -> dw_out (flat, Cout*KH*KW*Cin_real floats).
-    kreal = (KH, KW, Cin) of the real filter when x rows are padded im2col rows (stem)."""
+    kreal = (KH, KW, Cin) of the real filter when x rows are padded im2col rows (stem).  The launch is wgrad_path's."""
     n, h, w, cin = x.shape
     cout = dy.shape[-1]
     m = dy.numel() // cout
     lib = _hip.lib()
     assert tuple(dy.shape[:-1]) == (n, (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1), \
         f"dy {tuple(dy.shape)} is not the output of a {kh} x {kw} / stride {stride} / pad {pad} conv over x {tuple(x.shape)}"
-    if bf16 == 6 and not force_x6:
-        bf16 = False            # (see below)
     if _is_h(dy):
-        # precision-16 step with half tensors: the same two 16-bit kernels, their operands read as the halves they are stored as
         assert _is_h(x) and bf16 == 2 and kreal is None
-        if lib.ssad_wgrad3x3_g16_ok(cin, cout, kh, kw, stride, pad):
-            # 3 x 3 / pad 1, stride 1 or 2: tiles staged as they lie in memory, transposed by the fragment reads (csrc/wgrad16.hip)
-            ho, wo = dy.shape[1], dy.shape[2]
-            splits = lib.ssad_wgrad3x3_g16_splits(n, ho, wo, cin, cout, stride)
-            slab = _new((splits, cout, 9 * cin), dy)
-            _run("wgrad_g16", 2.0 * m * cout * 9 * cin, 2.0 * (dy.numel() + x.numel()) + 4.0 * slab.numel(),
-                 lambda: lib.ssad_conv_wgrad3x3_g16_h(dy.data_ptr(), x.data_ptr(), _hip.ptr(slab), splits, n, ho, wo, h, w, cin, cout,
-                                                      stride, dy.numel(), _hip.stream()))
-        elif lib.ssad_wgrad3x3_halo16_ok(cin, cout, kh, kw, stride, pad):
-            splits = lib.ssad_wgrad3x3_halo16_splits(n, h, w, cin, cout)
-            slab = _new((splits, cout, 9 * cin), dy)
-            _run("wgrad_h16", 2.0 * m * cout * 9 * cin, 2.0 * (dy.numel() + x.numel()) + 4.0 * slab.numel(),
-                 lambda: lib.ssad_conv_wgrad3x3_halo16_h(dy.data_ptr(), x.data_ptr(), _hip.ptr(slab), splits, n, h, w, cin, cout,
-                                                         dy.numel(), _hip.stream()))
-        else:
-            splits = lib.ssad_wgrad_splits_bf16(m, cin, cout, kh, kw)
-            slab = _new((splits, cout, kh * kw * cin), dy)
-            _run("wgrad_h16", 2.0 * m * cout * kh * kw * cin, 2.0 * (dy.numel() + x.numel()) * kh * kw + 4.0 * slab.numel(),
-                 lambda: lib.ssad_conv_wgrad_f16_h(dy.data_ptr(), x.data_ptr(), _hip.ptr(slab), splits, n, h, w, cin, cout, kh, kw,
-                                                   stride, pad, dy.numel(), _hip.stream()))
-        _wgrad_reduce(slab, dw_out, splits, cout, kh * kw * cin, kh, kw, cin, to_oihw, accumulate)
-        return dw_out
-    if (int(bf16) in (0, 1, 2) and not _is_h(dy) and kreal is None and kh == 1 and kw == 1 and h == 1 and w == 1
-            and m <= lib.ssad_linear_small_max_rows()):
+    path, _, splits = wgrad_path(dy.shape, x.shape, kh, kw, stride, pad, bf16, _is_h(dy), force_x6, kreal)
+    if bf16 == 6 and not force_x6:
+        # bf16x6 training keeps weight gradients on the exact fp32 kernel: the wave-specialised fp32 wgrad (110 TFLOP/s) is
+        # as fast as the six-product bf16 form (measured), and exact; ssad_conv_wgrad_x6 stays available (tests)
+        bf16 = False
+    if path.startswith("g16_"):
+        # precision-16 step with half tensors: 3 x 3 / pad 1, stride 1 or 2: tiles staged as they lie in memory, transposed by the
+        # fragment reads (csrc/wgrad16.hip)
+        ho, wo = dy.shape[1], dy.shape[2]
+        slab = _new((splits, cout, 9 * cin), dy)
+        _run("wgrad_g16", 2.0 * m * cout * 9 * cin, 2.0 * (dy.numel() + x.numel()) + 4.0 * slab.numel(),
+             lambda: lib.ssad_conv_wgrad3x3_g16_h(dy.data_ptr(), x.data_ptr(), _hip.ptr(slab), splits, n, ho, wo, h, w, cin, cout,
+                                                  stride, dy.numel(), _hip.stream()))
+    elif path == "halo16_h":
+        slab = _new((splits, cout, 9 * cin), dy)
+        _run("wgrad_h16", 2.0 * m * cout * 9 * cin, 2.0 * (dy.numel() + x.numel()) + 4.0 * slab.numel(),
+             lambda: lib.ssad_conv_wgrad3x3_halo16_h(dy.data_ptr(), x.data_ptr(), _hip.ptr(slab), splits, n, h, w, cin, cout,
+                                                     dy.numel(), _hip.stream()))
+    elif path == "generic_f16_h":
+        # the same 16-bit split kernel as the fp16-operand form, its operands read as the halves they are stored as
+        slab = _new((splits, cout, kh * kw * cin), dy)
+        _run("wgrad_h16", 2.0 * m * cout * kh * kw * cin, 2.0 * (dy.numel() + x.numel()) * kh * kw + 4.0 * slab.numel(),
+             lambda: lib.ssad_conv_wgrad_f16_h(dy.data_ptr(), x.data_ptr(), _hip.ptr(slab), splits, n, h, w, cin, cout, kh, kw,
+                                               stride, pad, dy.numel(), _hip.stream()))
+    elif path == "linear_small":
         # linear layer over a training batch's rows: one launch straight into the gradient (OIHW == OHWI for 1 x 1); the 16-bit modes
         # round the operands while they are loaded
         _run_aside("wgrad_f32" if not bf16 else "wgrad_small16", 2.0 * m * cout * cin, 4.0 * (dy.numel() + x.numel() + cout * cin),
                    lambda: lib.ssad_linear_wgrad_small_r(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(dw_out), m, cin, cout, int(accumulate), int(bf16),
                                                          _hip.stream()), keep=(dy, x))
         return dw_out
-    halo = (lib.ssad_wgrad3x3_halo_ok(cin, cout, kh, kw, stride, pad)
-            if not bf16 and kreal is None and os.environ.get("SSAD_WGRAD_HALO", "1") != "0" else 0)
-    if halo:
+    elif path.startswith("halo_s"):
         # 3x3 / pad 1 on the exact fp32 path: halo-tile kernel (one workgroup = a 64 x 64 block, all nine taps); stride 1 or 2
         ho, wo = dy.shape[1], dy.shape[2]
         assert (ho, wo) == ((h - 1) // stride + 1, (w - 1) // stride + 1)
-        splits = lib.ssad_wgrad3x3_halo_splits(n, ho, wo, cin, cout)
         slab = _new((splits, cout, 9 * cin), dy)
-        if halo == 1:
+        if path == "halo_s1":
             fn = lambda: lib.ssad_conv_wgrad3x3_halo(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(slab), splits, n, h, w, cin, cout,
                                                      dy.numel(), _hip.stream())
         else:
             fn = lambda: lib.ssad_conv_wgrad3x3s2_halo(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(slab), splits, n, ho, wo, h, w, cin,
                                                        cout, dy.numel(), _hip.stream())
         _run("wgrad_f32", 2.0 * m * cout * 9 * cin, 4.0 * (dy.numel() + x.numel() + slab.numel()), fn)
-        _wgrad_reduce(slab, dw_out, splits, cout, 9 * cin, 3, 3, cin, to_oihw, accumulate)
-        return dw_out
-    if bf16 in (1, 2, True) and kreal is None and lib.ssad_wgrad3x3_halo16_ok(cin, cout, kh, kw, stride, pad):
+    elif path.startswith("halo16_"):
         # 16-bit operands, 3x3 / stride 1 / pad 1: halo-tile kernel (dZ and X fetched, converted and transposed once per pixel tile
         # instead of once per filter tap; csrc/wgrad_halo16.hip)
-        splits = lib.ssad_wgrad3x3_halo16_splits(n, h, w, cin, cout)
         slab = _new((splits, cout, 9 * cin), dy)
         _run(_kname("wgrad", bf16), 2.0 * m * cout * 9 * cin, 4.0 * (dy.numel() + x.numel() + slab.numel()),
              lambda: lib.ssad_conv_wgrad3x3_halo16(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(slab), splits, n, h, w, cin, cout,
                                                    int(bf16 == 2), dy.numel(), _hip.stream()))
-        _wgrad_reduce(slab, dw_out, splits, cout, 9 * cin, 3, 3, cin, to_oihw, accumulate)
+    else:
+        assert path.startswith("generic_"), path
+        slab = _new((splits, cout, kh * kw * cin), dy)
+        fn = (lib.ssad_conv_wgrad_x6 if bf16 == 6 else lib.ssad_conv_wgrad_x3 if bf16 == 3 else
+              lib.ssad_conv_wgrad_f16 if bf16 == 2 else
+              lib.ssad_conv_wgrad_bf16 if bf16 else lib.ssad_conv_wgrad)
+        _run(_kname("wgrad", bf16), 2.0 * m * cout * kh * kw * cin,
+             4.0 * (dy.numel() * kh * kw + x.numel() * kh * kw + slab.numel()),
+             lambda: fn(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(slab), splits, n, h, w, cin, cout, kh, kw, stride, pad, dy.numel(),
+                        _hip.stream()))
+        rkh, rkw, rcin = kreal if kreal else (kh, kw, cin)
+        _wgrad_reduce(slab, dw_out, splits, cout, kh * kw * cin, rkh, rkw, rcin, to_oihw, accumulate)
         return dw_out
-    if bf16 == 6 and not force_x6:
-        # bf16x6 training keeps weight gradients on the exact fp32 kernel: the wave-specialised fp32 wgrad (110 TFLOP/s) is
-        # as fast as the six-product bf16 form (measured), and exact; ssad_conv_wgrad_x6 stays available (tests)
-        bf16 = False
-    splits = (_hip.lib().ssad_wgrad_splits_bf16 if bf16 else _hip.lib().ssad_wgrad_splits)(m, cin, cout, kh, kw)
-    slab = _new((splits, cout, kh * kw * cin), dy)
-    fn = (_hip.lib().ssad_conv_wgrad_x6 if bf16 == 6 else _hip.lib().ssad_conv_wgrad_x3 if bf16 == 3 else
-          _hip.lib().ssad_conv_wgrad_f16 if bf16 == 2 else
-          _hip.lib().ssad_conv_wgrad_bf16 if bf16 else _hip.lib().ssad_conv_wgrad)
-    _run(_kname("wgrad", bf16), 2.0 * m * cout * kh * kw * cin,
-         4.0 * (dy.numel() * kh * kw + x.numel() * kh * kw + slab.numel()),
-         lambda: fn(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(slab), splits, n, h, w, cin, cout, kh, kw, stride, pad, dy.numel(),
-                    _hip.stream()))
-    rkh, rkw, rcin = kreal if kreal else (kh, kw, cin)
-    _wgrad_reduce(slab, dw_out, splits, cout, kh * kw * cin, rkh, rkw, rcin, to_oihw, accumulate)
+    _wgrad_reduce(slab, dw_out, splits, cout, kh * kw * cin, kh, kw, cin, to_oihw, accumulate)
     return dw_out
+
+
+def stem_wgrad_path(img_shape, half=False):
+    """("stem", kernel, splits) of stem_wgrad over NCHW images of img_shape with dz stored as halves (half) or floats: kernel =
+    STEM_WGRAD_KERNELS[ssad_wgrad_variant_id(WGRAD_STEM, ...)], splits = the per-workgroup slabs ssad_wgrad_reduce sums."""
+    b, _, h, w = (int(v) for v in img_shape)
+    lib = _hip.lib()
+    return ("stem", STEM_WGRAD_KERNELS[lib.ssad_wgrad_variant_id(WGRAD_STEM, 0, 3, 64, 2, int(bool(half)))],
+            lib.ssad_stem_wgrad_splits(b, h, w))
 
 
 def stem_wgrad(img, dz, dw_out, to_oihw=False, accumulate=False):
@@ -951,8 +988,9 @@ def stem_wgrad(img, dz, dw_out, to_oihw=False, accumulate=False):
     _, _, _, ho, wo = stem_geometry(h, w, 0, 0)
     assert c == 3 and tuple(dz.shape) == (b, ho, wo, 64), f"dz {tuple(dz.shape)} does not belong to images {tuple(img.shape)}"
     lib = _hip.lib()
+    _, kernel, _ = stem_wgrad_path(img.shape, _is_h(dz))
     ws = torch.empty(lib.ssad_stem_wgrad_workspace(b, h, w), device=img.device, dtype=torch.float32)
-    if _is_h(dz):
+    if kernel != "float":
         _run("stem_wgrad_h16", 2.0 * dz.numel() * 147, 2.0 * dz.numel() + 4.0 * img.numel() * 1.6,
              lambda: lib.ssad_stem_wgrad_h(_hip.ptr(img), dz.data_ptr(), _hip.ptr(dw_out), b, h, w, dz.numel(), int(to_oihw), int(accumulate),
                                            _hip.ptr(ws), _hip.stream()))
