@@ -492,6 +492,16 @@ int ssad_cosine_knn_fused(const float* x, const float* bank_normalized, float* o
  * Bit-identical to ssad_cosine_knn_fused for every S.  D % 32 == 0, 1 <= S <= 65535. */
 int ssad_cosine_knn_split(const float* x, const float* bank_normalized, float* part, float* out, int64_t N, int D, int R, int k, int S,
                           void* stream);
+/* Greedy k-center (farthest-point) coreset of the kNN bank (PatchCore; csrc/coreset.hip; the reference has no coreset) over the
+ * rows of p [R][d] (fp32, row-major), squared Euclidean distance sum_j (p[r][j] - p[c][j])^2 summed as a direct sum of squared
+ * differences in one fixed order per row.  sel[0] = start; sel[t] = argmax_r min_{s<t} dist(r, sel[s]), ties to the smallest row;
+ * rad[t] = that maximum (rad[0] = +inf).  Stops early when the maximum reaches 0 (every row lies on a centre): *m_out (written on
+ * the device, read by the caller after the stream) is the number of centres recorded, <= min(m, R).  One launch per step on
+ * `wgs` workgroups of contiguous rows, the last step on one; no atomics.  sel, rad and *m_out are the same bits for every wgs.
+ * Workspace (caller-owned): mind [R] floats, part [2][wgs] (float value, int32 row) pairs.  sel / rad hold min(m, R) entries.
+ * d % 4 == 0, 4 <= d <= 1024, p 16-byte aligned, finite rows. */
+int ssad_coreset_greedy(const float* p, int64_t R, int d, int m, int64_t start, int wgs, float* mind, void* part, int64_t* sel,
+                        float* rad, int* m_out, void* stream);
 /* Gaussian density estimator (GDE) scorer of CutPaste (csrc/gde.hip; the reference has no such scorer).
  * ssad_gaussian_fit_stats: of the N rows of x [N][D] (each first L2-normalised bit-identically to ssad_l2_normalize_rows when
  * `normalize`), in fp64: mean[D], scatter[D][D] = sum_i (x_i - mean)(x_i - mean)^T and m4[0] = sum_i ||x_i - mean||^4 (the sufficient

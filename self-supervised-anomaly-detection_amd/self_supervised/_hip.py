@@ -47,6 +47,7 @@ SIGNATURES = {
     "ssad_cosine_knn_mean": [_c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
     "ssad_cosine_knn_fused": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     "ssad_cosine_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_coreset_greedy": [_c_fp, _c_l, _c_i, _c_i, _c_l, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_gaussian_fit_stats": [_c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_mahalanobis_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
     "ssad_blur_relu_bilinear": [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],

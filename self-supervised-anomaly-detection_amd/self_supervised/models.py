@@ -345,19 +345,80 @@ def _take(t, idx):
     return t[torch.as_tensor(idx, dtype=torch.int64, device=t.device)]
 
 
+CORESET_SEED = 20230611   # seed of the coreset projection's own CPU generator
+_CORESET_OMEGA = {}
+
+
+def coreset_projection(D, d):
+    """Omega [D][d] of the coreset selection (PatchCore's random projection): N(0, 1/d) entries drawn from a dedicated CPU
+    torch.Generator seeded with CORESET_SEED, cached per (D, d).  Never draws from the global torch, numpy or `random` generators, so
+    the reference's draw order (quirk Q5, the 70/30 split) does not move."""
+    key = (int(D), int(d))
+    if key not in _CORESET_OMEGA:
+        g = torch.Generator(device="cpu").manual_seed(CORESET_SEED)
+        _CORESET_OMEGA[key] = torch.randn(key, generator=g, dtype=torch.float64).div_(np.sqrt(key[1])).float()
+    return _CORESET_OMEGA[key]
+
+
+def check_coreset(coreset, coreset_dim=128):
+    """ValueError unless `coreset` is None, a fraction in (0, 1] or an int >= 1, and `coreset_dim` None or a multiple of 4 in 4..1024."""
+    if coreset is not None:
+        if isinstance(coreset, (bool, np.bool_)) or not isinstance(coreset, (int, float, np.integer, np.floating)):
+            raise ValueError(f"coreset must be None, a fraction in (0, 1] or an int >= 1, got {coreset!r}")
+        if isinstance(coreset, (int, np.integer)):
+            if coreset < 1:
+                raise ValueError(f"coreset must be an int >= 1 (rows) or a fraction in (0, 1], got {coreset!r}")
+        elif not 0.0 < coreset <= 1.0:
+            raise ValueError(f"coreset as a fraction must lie in (0, 1], got {coreset!r}")
+    if coreset_dim is not None:
+        if isinstance(coreset_dim, (bool, np.bool_)) or not isinstance(coreset_dim, (int, np.integer)) \
+                or not (4 <= coreset_dim <= 1024 and coreset_dim % 4 == 0):
+            raise ValueError(f"coreset_dim must be None or a multiple of 4 in 4..1024, got {coreset_dim!r}")
+    return coreset
+
+
+def coreset_size(coreset, r):
+    """Rows m the coreset keeps of r: ceil(f * r) for a fraction f, the int itself otherwise (m >= r: the whole bank)."""
+    if isinstance(coreset, (int, np.integer)):
+        return int(coreset)
+    return int(np.ceil(float(coreset) * int(r)))
+
+
+def coreset_select(bank_n, m, coreset_dim=128):
+    """Greedy k-center coreset of the L2-normalised bank rows bank_n [R][D] (PatchCore): the selection runs on bank_n Omega
+    (coreset_projection(D, coreset_dim), one MFMA GEMM) or, with coreset_dim None, on bank_n itself, starting from row 0.
+    Returns (sel int64 [m'] in selection order, rad float32 [m']) on the bank's device (ops.coreset_greedy)."""
+    if coreset_dim is None:
+        p = bank_n
+    else:
+        omega_t = coreset_projection(bank_n.shape[1], coreset_dim).t().contiguous().to(bank_n.device)
+        p = ops.linear_fwd(bank_n, omega_t)
+    return ops.coreset_greedy(p, m, start=0)
+
+
 class AnomalyDetector:
     """src/self_supervised/models.py:345-370: cosine 3-NN distance to a bank of normal embeddings.
 
     ``fit`` keeps the reference's unseeded 70/30 split (quirk Q5: depends on the global numpy RNG);
-    the bank is L2-normalised once and kept on the GPU, ``predict`` = normalise + MFMA GEMM + top-3 mean."""
+    the bank is L2-normalised once and kept on the GPU, ``predict`` = normalise + MFMA GEMM + top-3 mean.
 
-    def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None) -> None:
+    `coreset` (opt-in; the reference keeps every row): None = the exact bank; a fraction f in (0, 1] or an int m >= 1 = ``fit`` keeps
+    m = ceil(f R) (or m) of the R bank rows left after the split, chosen by a greedy k-center selection (coreset_select) on the
+    normalised rows projected to `coreset_dim` dimensions (None: unprojected).  The bank is then those full-dimension normalised rows
+    in selection order, and the threshold is scored against it.  m >= R launches nothing: the exact bank."""
+
+    def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
+                 coreset_dim: int = 128) -> None:
         self.patch_level = patch_level
         self.batch = batch
         self.dim = int(np.sqrt(num_patches)) if num_patches else None
         self.k = 3
         self.bank = None
         self.threshold = None
+        self.coreset = check_coreset(coreset, coreset_dim)
+        self.coreset_dim = coreset_dim
+        self.coreset_rows = None        # after fit with a coreset: (sel, rad) -- sel indexes the bank rows after the split
+        self.coreset_counts = None      # after fit with a coreset: (rows kept, rows after the split)
 
     @staticmethod
     def _dev(t):
@@ -379,6 +440,14 @@ class AnomalyDetector:
             train, val = emb, emb
         self.k = 3
         self.fit_bank(train)
+        if self.coreset is not None:
+            r = int(self.bank.shape[0])
+            m = coreset_size(self.coreset, r)
+            if m < r:
+                sel, rad = coreset_select(self.bank, m, self.coreset_dim)
+                self.bank = self.bank.index_select(0, sel).contiguous()
+                self.coreset_rows = (sel, rad)
+            self.coreset_counts = (int(self.bank.shape[0]), r)
         scores = self._scores(self._dev(val))
         self.threshold = torch.max(scores).item()
 

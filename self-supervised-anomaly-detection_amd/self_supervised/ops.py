@@ -689,6 +689,42 @@ def cosine_knn_split(x, bank_n, k=3, splits=1):
     return out
 
 
+CORESET_MAX_WGS = 1024    # workgroups of a coreset step: 4 per CU of an MI355X (256 CUs), all resident in one round
+CORESET_ROWS_PER_WG = 128  # rows a workgroup keeps at the least (one pass of the kernel's 128-row tile)
+
+
+def coreset_workgroups(r):
+    """Default workgroup count of coreset_greedy for r rows: enough workgroups of >= CORESET_ROWS_PER_WG rows, at most
+    CORESET_MAX_WGS.  The selection is the same bits for every count."""
+    return max(1, min(CORESET_MAX_WGS, -(-int(r) // CORESET_ROWS_PER_WG)))
+
+
+def coreset_greedy(p, m, start=0, wgs=None):
+    """Greedy k-center (farthest-point) selection over the rows of p [R][d] (csrc/coreset.hip ssad_coreset_greedy): sel[0] = start,
+    sel[t] = the row farthest (squared Euclidean distance) from its nearest earlier centre, ties to the smallest row; rad[t] = that
+    distance (rad[0] = inf).  Stops early when every row lies on a centre.  Returns (sel int64 [m'], rad float32 [m']), m' <= min(m, R),
+    on p's device; one launch per step, one host sync at the end.  `wgs`: workgroup count (default coreset_workgroups(R))."""
+    r, d = p.shape
+    m, start = int(m), int(start)
+    if m < 1:
+        raise ValueError(f"coreset_greedy: m must be >= 1, got {m}")
+    if not 0 <= start < r:
+        raise ValueError(f"coreset_greedy: start {start} is not a row of the {r} rows")
+    g = coreset_workgroups(r) if wgs is None else int(wgs)
+    steps = min(m, r)
+    mind = _new((r,), p)
+    part = torch.empty((2, g), device=p.device, dtype=torch.int64)      # (float value, int32 row) pairs
+    sel = torch.empty((steps,), device=p.device, dtype=torch.int64)
+    rad = _new((steps,), p)
+    m_out = torch.zeros((1,), device=p.device, dtype=torch.int32)
+    _run("coreset_greedy", 3.0 * steps * r * d, 4.0 * steps * r * d,
+         lambda: _hip.lib().ssad_coreset_greedy(_hip.ptr(p), r, d, m, start, g, _hip.ptr(mind), _hip.ptr(part, dtype=torch.int64),
+                                                _hip.ptr(sel, dtype=torch.int64), _hip.ptr(rad), _hip.ptr(m_out, dtype=torch.int32),
+                                                _hip.stream()))
+    n = int(m_out.item())
+    return sel[:n], rad[:n]
+
+
 def cosine_knn_fused(x, bank_n, k=3):
     """x [N][D] (not normalised), bank_n [R][D] L2-normalised -> [N] mean of the k smallest cosine distances, one kernel; split over
     the bank rows (cosine_knn_split, same bits) when few queries meet a large bank (knn_splits)."""

@@ -17,7 +17,7 @@ from . import metrics as mtr
 from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
-from .models import AnomalyDetector, GaussianDensityDetector, PeraNet
+from .models import AnomalyDetector, GaussianDensityDetector, PeraNet, check_coreset
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -373,6 +373,20 @@ def _check_bank(bank, mvtec_inference=True):
     return bank
 
 
+def _check_coreset(coreset, detector):
+    """The coreset option of the kNN detector (models.check_coreset); the Gaussian is fitted on every row -- cheap, and a coreset
+    would bias its covariance."""
+    if coreset is not None and detector == 'gde':
+        raise ValueError("coreset applies to detector='knn' only: the Gaussian density detector is fitted on every row")
+    return check_coreset(coreset)
+
+
+def _print_coreset(detector):
+    counts = getattr(detector, "coreset_counts", None)
+    if counts is not None:
+        print(f' coreset: {counts[0]} of {counts[1]} rows')
+
+
 def _embed_files(model, tester, dataset, files):
     """Embeddings of `files` (per image: [patches][D], in order) through ``Trainer.predict`` over an UNSHUFFLED loader of batch size 1
     with the test dataset's transform -- the route for training images when the streamed predict is off."""
@@ -400,14 +414,18 @@ def _train_bank_rows(per_image, n_total, device):
 
 
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
-              patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference') -> ModelOutputsContainer:
+              patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
+              coreset=None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
     (quirks Q3 / Q4), so image-level 'gde' raises.  'train' = every image of train/good in file order (one row per image at image
-    level, its patches at patch level), the 70/30 split drawn over images; MVTec data only."""
+    level, its patches at patch level), the 70/30 split drawn over images; MVTec data only.
+    `coreset`: None (default) = the kNN bank keeps every row; a fraction in (0, 1] or an int >= 1 = a greedy k-center coreset of
+    that many of the bank rows left after the split (AnomalyDetector(coreset=...)); 'knn' only."""
     scorer = _check_detector(detector)
     _check_bank(bank, mvtec_inference)
+    _check_coreset(coreset, scorer)
     whole = bank == 'train'
     del TIMELINE[:]
     print('>>> initializing inference')
@@ -493,10 +511,11 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     print('>>> anomaly detection phase')
     groups = None
     kind = GaussianDensityDetector if scorer == 'gde' else AnomalyDetector
+    det_kw = {} if coreset is None else {"coreset": coreset}
     if patch_localization:
-        detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches)
+        detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches, **det_kw)
     else:
-        detector = kind()
+        detector = kind(**det_kw)
     if whole:
         # the training images' embeddings: from the stream (in front of the test images) or, with the streamed predict off or no test
         # images on this rank, from Trainer.predict over an unshuffled loader -- the same rows either way
@@ -556,6 +575,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         # of the Gaussian for 'gde'
         if rank == 0:
             detector.fit(normality, **fit_kw)
+            _print_coreset(detector)
             payload = (detector.state() if scorer == 'gde' else detector.bank.cpu(), detector.threshold)
         state = broadcast_bank(payload if rank == 0 else None)
         if rank != 0:
@@ -567,6 +587,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
                 detector.bank, detector.threshold = AnomalyDetector._dev(state[0]), state[1]
     else:
         detector.fit(normality, **fit_kw)
+        _print_coreset(detector)
     _mark("bank-fitted")
     print(' computing anomaly scores')
     output.anomaly_maps = detector.predict(emb_dev if emb_dev is not None else output.embedding_vectors).cpu()
@@ -615,14 +636,15 @@ def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64)
 def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = (256, 256), patch_localization: bool = True,
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
-          detector: str = 'knn', bank: str = 'reference'):
+          detector: str = 'knn', bank: str = 'reference', coreset=None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
-    category.  Returns the pandas DataFrame (identical on every rank).  `detector` and `bank` as in `inference`."""
+    category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank` and `coreset` as in `inference`."""
     _check_detector(detector)
     _check_bank(bank)
+    _check_coreset(coreset, detector)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows = {}
@@ -635,7 +657,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
                          batch_size=batch_size, projection_training_params=projection_training_params,
                          fine_tune_params=fine_tune_params, trainer_kwargs=trainer_kwargs)
             out = inference(sub_out + 'best_model.ckpt', data, subject, mvtec_inference=True,
-                            patch_localization=patch_localization, detector=detector, bank=bank)
+                            patch_localization=patch_localization, detector=detector, bank=bank, coreset=coreset)
         if patch_localization:
             out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False)      # stays on the device: the Evaluator's GPU metrics
         ev = Evaluator(evaluation_metrics=[m for m in metrics if (m != 'f1-score') == patch_localization or m == 'auroc'])

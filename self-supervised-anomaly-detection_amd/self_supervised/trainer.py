@@ -377,8 +377,8 @@ def gather_in_order(local_items, total):
 def broadcast_bank(obj, src=0):
     """The normality bank (plus its threshold) is fitted on one rank -- the 70/30 split draws from the global numpy RNG -- and sent
     to the others once: <= 1000 x 512 fp32 with the reference's bank, the 70 % of the whole training set with
-    tools.inference(bank='train') (123 k x 512 fp32 = 250 MB for bottle's patches).  `obj` is any picklable object on `src`, ignored
-    elsewhere."""
+    tools.inference(bank='train') (123 k x 512 fp32 = 250 MB for bottle's patches; a tenth of that with coreset=0.1).  `obj` is any
+    picklable object on `src`, ignored elsewhere."""
     rank, world = world_info()
     if world == 1:
         return obj
