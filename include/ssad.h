@@ -492,6 +492,33 @@ int ssad_cosine_knn_fused(const float* x, const float* bank_normalized, float* o
  * Bit-identical to ssad_cosine_knn_fused for every S.  D % 32 == 0, 1 <= S <= 65535. */
 int ssad_cosine_knn_split(const float* x, const float* bank_normalized, float* part, float* out, int64_t N, int D, int R, int k, int S,
                           void* stream);
+/* kneighbors of the cosine bank (sklearn NearestNeighbors.kneighbors, which the reference's AnomalyDetector wraps, models.py:352-370,
+ * returns (distances, indices); the two entries above keep the distances only).  Adds WHICH bank rows are the nearest: for every query
+ * the k (1..3) smallest (distance, bank row) pairs in lexicographic order, ascending -- dist [N][k] float32, idx [N][k] int32; equal
+ * distances go to the smaller row.  Tile, K order and distance expression of ssad_cosine_knn_fused: the distances are the bits it
+ * averages.  ssad_cosine_knn_index: one launch.  ssad_cosine_knn_index_split: the bank split of ssad_cosine_knn_split, part [S][N][3]
+ * 64-bit keys (caller-owned, 8-byte aligned; not read for S = 1) + a merge launch.  No atomics; dist and idx are the same bits for
+ * every S and on every call.  D % 32 == 0, D <= 65536, k <= R, 1 <= S <= 65535. */
+int ssad_cosine_knn_index(const float* x, const float* bank_normalized, float* dist, int* idx, int64_t N, int D, int R, int k,
+                          void* stream);
+int ssad_cosine_knn_index_split(const float* x, const float* bank_normalized, void* part, float* dist, int* idx, int64_t N, int D, int R,
+                                int k, int S, void* stream);
+/* Image scores at patch level (csrc/image_score.hip; PatchCore eq. 6-7 on cosine distances; the reference's patch-level branch
+ * returns maps only).
+ * ssad_rows_smallest_index adds a partial row sort: the bp = min(b, R) smallest (value, column) pairs of each row of m [Q][R],
+ *   ascending, lexicographic (numpy's stable argsort; -0 counts as +0; no NaNs) -> vals [Q][bp], cols [Q][bp].  cosine != 0: the value
+ *   of a column is clip(1 - m[q][c], 0, 2) (m holds similarities).  wgs workgroups per row over contiguous column ranges + one merge
+ *   workgroup per row; part [Q][wgs][b] 64-bit keys (caller-owned, 8-byte aligned).  The result does not depend on wgs.
+ *   1 <= b <= 32, 1 <= wgs <= 4096 / b, Q <= 65535.
+ * ssad_rows_argmax adds a row maximum with its position: val[q] = max_p s[q][p], flat[q] = q P + the smallest p that reaches it.
+ * ssad_knn_reweight adds the weight: out[q] = (1 - exp(d(x_q, mstar[q])) / sum_{j < bp} exp(d(x_q, nbr[q][j]))) smax[q] with
+ *   d(x, r) = clip(1 - <x / ||x||, bank_r>, 0, 2), xs [Q][D] not normalised, bank L2-normalised, mstar [Q] and nbr [Q][bp] bank rows
+ *   (a row outside 0 .. R - 1 counts as distance 1).  1 <= bp <= 32.  Fixed-order sums: the same bits on every call. */
+int ssad_rows_smallest_index(const float* m, int64_t Q, int R, int b, int cosine, int wgs, void* part, float* vals, int* cols,
+                             void* stream);
+int ssad_rows_argmax(const float* s, int64_t Q, int P, float* val, int64_t* flat, void* stream);
+int ssad_knn_reweight(const float* xs, const float* bank_normalized, const int* mstar, const int* nbr, const float* smax, float* out,
+                      int64_t Q, int D, int R, int bp, void* stream);
 /* Greedy k-center (farthest-point) coreset of the kNN bank (PatchCore; csrc/coreset.hip; the reference has no coreset) over the
  * rows of p [R][d] (fp32, row-major), squared Euclidean distance sum_j (p[r][j] - p[c][j])^2 summed as a direct sum of squared
  * differences in one fixed order per row.  sel[0] = start; sel[t] = argmax_r min_{s<t} dist(r, sel[s]), ties to the smallest row;

@@ -7,17 +7,19 @@ from torch import Tensor
 _FIELDS = ("original_data", "tensor_data", "y_true_binary_labels", "raw_predictions", "y_hat",
            "y_true_multiclass_labels", "ground_truths", "anomaly_maps", "embedding_vectors")
 _OPTIONAL_IN_CAT = ("ground_truths", "anomaly_maps")
+# carried beside the reference's nine fields, one row per image: tools.inference(image_scores=...) fills it, None otherwise
+_PER_IMAGE_EXTRA = ("image_scores",)
 
 
 class ModelOutputsContainer:
     """The 9 tensor fields ``predict_step`` / ``tools.inference`` hand around (constants.py:7-53)."""
 
     def __init__(self) -> None:
-        for f in _FIELDS:
+        for f in _FIELDS + _PER_IMAGE_EXTRA:
             setattr(self, f, None)
 
     def to_cpu(self):
-        for f in _FIELDS:
+        for f in _FIELDS + _PER_IMAGE_EXTRA:
             v = getattr(self, f)
             setattr(self, f, v.to('cpu') if torch.is_tensor(v) else None)
 
@@ -32,7 +34,9 @@ class ModelOutputsContainer:
                 cols[f].append(v)
         for f in _FIELDS:
             setattr(self, f, torch.cat(cols[f]) if len(cols[f]) else None)
-
+        for f in _PER_IMAGE_EXTRA:
+            vals = [getattr(p, f, None) for p in predictions]
+            setattr(self, f, torch.cat(vals) if vals and all(torch.is_tensor(v) for v in vals) else None)
 
     def split(self, n_images: int) -> list:
         """One container per image: the inverse of ``from_list`` for a container that holds ``n_images`` images
@@ -47,6 +51,10 @@ class ModelOutputsContainer:
                     setattr(c, f, v[i * k:(i + 1) * k].clone())
                 else:
                     setattr(c, f, v)
+            for f in _PER_IMAGE_EXTRA:
+                v = getattr(self, f, None)
+                if torch.is_tensor(v):
+                    setattr(c, f, v[i:i + 1].clone())
             parts.append(c)
         return parts
 

@@ -377,6 +377,20 @@ def check_coreset(coreset, coreset_dim=128):
     return coreset
 
 
+IMAGE_SCORES = (None, 'max', 'reweighted')
+
+
+def check_image_scores(image_scores, neighbours=9):
+    """ValueError unless `image_scores` is None, 'max' or 'reweighted' and, for 'reweighted', `neighbours` an int in 2..32 (one
+    neighbour gives the weight 0 by the formula)."""
+    if image_scores not in IMAGE_SCORES:
+        raise ValueError(f"image_scores must be one of {IMAGE_SCORES}, got {image_scores!r}")
+    if image_scores == 'reweighted':
+        if isinstance(neighbours, (bool, np.bool_)) or not isinstance(neighbours, (int, np.integer)) or not 2 <= neighbours <= 32:
+            raise ValueError(f"neighbours must be an int in 2..32 for image_scores='reweighted', got {neighbours!r}")
+    return image_scores
+
+
 def coreset_size(coreset, r):
     """Rows m the coreset keeps of r: ceil(f * r) for a fraction f, the int itself otherwise (m >= r: the whole bank)."""
     if isinstance(coreset, (int, np.integer)):
@@ -471,6 +485,44 @@ class AnomalyDetector:
         if self.patch_level:
             anomaly_scores = torch.reshape(anomaly_scores, (self.batch, 1, self.dim, self.dim))
         return anomaly_scores
+
+    def kneighbors(self, x: Tensor, k: int = None):
+        """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
+        idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by cosine distance, nearest first, equal
+        distances to the smaller row.  idx indexes self.bank (after the split and the coreset).  Works at both levels."""
+        if self.bank is None:
+            raise ValueError("kneighbors: the detector has no bank (fit or fit_bank first)")
+        x = self._dev(x)
+        if x.shape[1] % 32:
+            raise ValueError(f"kneighbors: the index kernel needs an embedding width that is a multiple of 32, got {x.shape[1]}")
+        dist, idx = ops.cosine_knn_index(x, self.bank, self.k if k is None else k)
+        return dist, idx.long()
+
+    def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = 9, scores: Tensor = None) -> Tensor:
+        """One score per image from the patch scores (patch level only; PatchCore eq. 6-7 with the cosine distance).  x [batch * P][D]
+        patch embeddings, image after image.  s_p = the patch scores predict returns (`scores`: that map, when the caller has it
+        already); p* = argmax_p s_p, the smallest p on ties.
+        'max': s_{p*}.  'reweighted': w s_{p*}, w = 1 - exp(d(x_{p*}, m*)) / sum_{r in N} exp(d(x_{p*}, r)) with m* the nearest
+        bank row of x_{p*} and N the min(neighbours, R) bank rows nearest to B_{m*} (2 <= neighbours <= 32).  Returns [batch]."""
+        check_image_scores(mode, neighbours)
+        if not self.patch_level or not self.dim:
+            raise ValueError("image_scores needs a patch-level detector (patch_level=True with num_patches)")
+        if self.bank is None:
+            raise ValueError("image_scores: the detector has no bank (fit or fit_bank first)")
+        x = self._dev(x)
+        p = self.dim * self.dim
+        if x.shape[0] % p:
+            raise ValueError(f"image_scores: {x.shape[0]} rows are not whole images of {p} patches")
+        s = self._scores(x) if scores is None else self._dev(scores)
+        smax, flat = ops.rows_argmax(s.reshape(x.shape[0] // p, p))
+        if mode == 'max':
+            return smax
+        xs = x.index_select(0, flat)                                     # x_{p*} of every image
+        _, mstar = ops.cosine_knn_index(xs, self.bank, 1)                # m*: an index pass over one row per image
+        centre = self.bank.index_select(0, mstar.reshape(-1).long())     # B_{m*}
+        sim = ops.linear_fwd(centre, self.bank)                          # [batch][R] similarities of B_{m*} to the bank
+        _, nbr = ops.rows_smallest_index(sim, neighbours, cosine=True)   # N: the rows nearest to B_{m*}
+        return ops.knn_reweight(xs, self.bank, mstar, nbr, smax)
 
 
 from .density import GaussianDensityDetector  # noqa: E402,F401  (opt-in second scorer: Ledoit-Wolf Gaussian, Mahalanobis distance)

@@ -739,6 +739,94 @@ def cosine_knn_fused(x, bank_n, k=3):
     return out
 
 
+def cosine_knn_index(x, bank_n, k=3, splits=None):
+    """kneighbors of the cosine bank: x [N][D] (not normalised), bank_n [R][D] L2-normalised -> (dist [N][k] float32, idx [N][k]
+    int32), the k (1..3) smallest (distance, bank row) pairs of every query, ascending, equal distances to the smaller row
+    (csrc/knn.hip ssad_cosine_knn_index / _split).  The distances are the bits cosine_knn_fused averages.  `splits`: None = the
+    knn_splits rule of cosine_knn_fused; S >= 1 = that many bank splits (1: the one-launch kernel); same bits for every S."""
+    n, d = x.shape
+    r = bank_n.shape[0]
+    k = int(k)
+    if not 1 <= k <= 3:
+        raise ValueError(f"cosine_knn_index: k must be 1, 2 or 3, got {k}")
+    if r < k:
+        raise ValueError(f"cosine_knn_index: the bank has {r} rows, fewer than k = {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"cosine_knn_index: splits must be >= 1, got {s}")
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    i32 = torch.int32
+    if s == 1:
+        _run("knn_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + 2 * n * k),
+             lambda: _hip.lib().ssad_cosine_knn_index(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d, r, k,
+                                                      _hip.stream()))
+        return dist, idx
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64)       # (distance bits << 32 | row) keys
+    _run("knn_index_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + 2 * n * k) + 16.0 * part.numel(),
+         lambda: _hip.lib().ssad_cosine_knn_index_split(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(part, dtype=torch.int64), _hip.ptr(dist),
+                                                        _hip.ptr(idx, dtype=i32), n, d, r, k, s, _hip.stream()))
+    return dist, idx
+
+
+ROWS_SMALLEST_COLS_PER_WG = 4096   # columns a workgroup of rows_smallest_index scans at the least (16 per thread and round)
+ROWS_SMALLEST_MAX_KEYS = 4096      # keys the merge workgroup of a row takes: wgs * b stays below
+
+
+def rows_smallest_workgroups(r, b):
+    """Default workgroups per row of rows_smallest_index for r columns: one per ROWS_SMALLEST_COLS_PER_WG columns, at most
+    ROWS_SMALLEST_MAX_KEYS // b.  The result is the same for every count."""
+    return max(1, min(ROWS_SMALLEST_MAX_KEYS // int(b), -(-int(r) // ROWS_SMALLEST_COLS_PER_WG)))
+
+
+def rows_smallest_index(m, b, cosine=False, wgs=None):
+    """The min(b, R) smallest (value, column) pairs of each row of m [Q][R], ascending, lexicographic -- the first entries of a
+    stable argsort (csrc/image_score.hip ssad_rows_smallest_index): (vals [Q][b'] float32, cols [Q][b'] int32).  cosine: m holds
+    similarities and the values are the cosine distances clip(1 - m, 0, 2).  b in 1..32; `wgs`: workgroups per row (default
+    rows_smallest_workgroups), 1 .. 4096 // b -- the same result for every count."""
+    q, r = m.shape
+    b = int(b)
+    if not 1 <= b <= 32:
+        raise ValueError(f"rows_smallest_index: b must lie in 1..32, got {b}")
+    g = rows_smallest_workgroups(r, b) if wgs is None else int(wgs)
+    if not 1 <= g <= ROWS_SMALLEST_MAX_KEYS // b:
+        raise ValueError(f"rows_smallest_index: wgs must lie in 1..{ROWS_SMALLEST_MAX_KEYS // b} for b = {b}, got {g}")
+    bp = min(b, r)
+    vals = _new((q, bp), m)
+    cols = torch.empty((q, bp), device=m.device, dtype=torch.int32)
+    part = torch.empty((q, g, b), device=m.device, dtype=torch.int64)
+    _run("rows_smallest", 0.0, 4.0 * b * m.numel() + 16.0 * part.numel(),
+         lambda: _hip.lib().ssad_rows_smallest_index(_hip.ptr(m), q, r, b, int(bool(cosine)), g, _hip.ptr(part, dtype=torch.int64),
+                                                     _hip.ptr(vals), _hip.ptr(cols, dtype=torch.int32), _hip.stream()))
+    return vals, cols
+
+
+def rows_argmax(s):
+    """s [Q][P] -> (val [Q] float32: the largest entry of each row, flat [Q] int64: q P + its column, the smallest column among equal
+    entries) -- csrc/image_score.hip ssad_rows_argmax."""
+    q, p = s.shape
+    val = _new((q,), s)
+    flat = torch.empty((q,), device=s.device, dtype=torch.int64)
+    _run("rows_argmax", 0.0, 4.0 * s.numel(),
+         lambda: _hip.lib().ssad_rows_argmax(_hip.ptr(s), q, p, _hip.ptr(val), _hip.ptr(flat, dtype=torch.int64), _hip.stream()))
+    return val, flat
+
+
+def knn_reweight(xs, bank_n, mstar, nbr, smax):
+    """PatchCore's image-score weight on cosine distances (csrc/image_score.hip ssad_knn_reweight): xs [Q][D] (not normalised),
+    bank_n [R][D] L2-normalised, mstar [Q] / [Q][1] int32 nearest bank rows, nbr [Q][b'] int32 neighbourhood rows, smax [Q] ->
+    [Q]: (1 - exp(d(x, mstar)) / sum_j exp(d(x, nbr_j))) smax."""
+    q, d = xs.shape
+    r = bank_n.shape[0]
+    bp = nbr.shape[1]
+    out = _new((q,), xs)
+    i32 = torch.int32
+    _run("knn_reweight", 2.0 * q * d * (bp + 1), 4.0 * q * d * (bp + 2),
+         lambda: _hip.lib().ssad_knn_reweight(_hip.ptr(xs), _hip.ptr(bank_n), _hip.ptr(mstar, dtype=i32), _hip.ptr(nbr, dtype=i32),
+                                              _hip.ptr(smax), _hip.ptr(out), q, d, r, bp, _hip.stream()))
+    return out
+
+
 def gaussian_fit_stats(x, normalize=True):
     """x [N][D] fp32 -> (mean [D], scatter [D][D], m4 [1]) fp64 of its rows (L2-normalised first when `normalize`): the centred
     sufficient statistics of a Ledoit-Wolf Gaussian fit (csrc/gde.hip), deterministic."""

@@ -17,7 +17,7 @@ from . import metrics as mtr
 from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
-from .models import AnomalyDetector, GaussianDensityDetector, PeraNet, check_coreset
+from .models import AnomalyDetector, GaussianDensityDetector, PeraNet, check_coreset, check_image_scores
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -381,6 +381,17 @@ def _check_coreset(coreset, detector):
     return check_coreset(coreset)
 
 
+def _check_image_scores(image_scores, neighbours, patch_localization, detector):
+    """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
+    scores and their nearest bank rows, which the image level and the Gaussian do not have."""
+    check_image_scores(image_scores, neighbours)
+    if image_scores is not None and not patch_localization:
+        raise ValueError("image_scores needs patch_localization=True: the image level scores images already")
+    if image_scores is not None and detector == 'gde':
+        raise ValueError("image_scores applies to detector='knn' only: a Gaussian patch score has no nearest bank row")
+    return image_scores
+
+
 def _print_coreset(detector):
     counts = getattr(detector, "coreset_counts", None)
     if counts is not None:
@@ -415,17 +426,22 @@ def _train_bank_rows(per_image, n_total, device):
 
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
-              coreset=None) -> ModelOutputsContainer:
+              coreset=None, image_scores: str = None, neighbours: int = 9) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
     (quirks Q3 / Q4), so image-level 'gde' raises.  'train' = every image of train/good in file order (one row per image at image
     level, its patches at patch level), the 70/30 split drawn over images; MVTec data only.
     `coreset`: None (default) = the kNN bank keeps every row; a fraction in (0, 1] or an int >= 1 = a greedy k-center coreset of
-    that many of the bank rows left after the split (AnomalyDetector(coreset=...)); 'knn' only."""
+    that many of the bank rows left after the split (AnomalyDetector(coreset=...)); 'knn' only.
+    `image_scores`: None (default) = maps only, as the reference; 'max' / 'reweighted' = the container also carries
+    `image_scores` [n_images] (test-set file order): the largest raw patch score of every image, for 'reweighted' weighted by the
+    `neighbours` (2..32, default 9) bank rows around its nearest bank row (AnomalyDetector.image_scores; PatchCore eq. 6-7).  Needs
+    patch_localization=True and detector='knn'; the maps are unchanged."""
     scorer = _check_detector(detector)
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, scorer)
+    _check_image_scores(image_scores, neighbours, patch_localization, scorer)
     whole = bank == 'train'
     del TIMELINE[:]
     print('>>> initializing inference')
@@ -590,8 +606,14 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         _print_coreset(detector)
     _mark("bank-fitted")
     print(' computing anomaly scores')
-    output.anomaly_maps = detector.predict(emb_dev if emb_dev is not None else output.embedding_vectors).cpu()
+    scored = emb_dev if emb_dev is not None else output.embedding_vectors
+    maps = detector.predict(scored)
+    output.anomaly_maps = maps.cpu()
     _mark("maps")
+    if image_scores is not None:
+        # from the raw maps that are still on the device; travels with its image through the exchange below
+        output.image_scores = detector.image_scores(scored, image_scores, neighbours, scores=maps.reshape(-1)).cpu()
+        _mark("image-scores")
     if world > 1:
         n_total = len(datamodule.test_dataset)
         per_image = gather_in_order(_split_container(output, n_pred), n_total)
@@ -616,6 +638,19 @@ def upsample(anomaly_maps: Tensor, target_size: int = 256, verbose: bool = True)
     return ops.blur_relu_bilinear(m.contiguous(), 7, target_size)
 
 
+def image_auroc(output: ModelOutputsContainer) -> float:
+    """Image AUROC of a patch-level run: the labels against `output.image_scores` (tools.inference(image_scores=...)), on the device
+    when the scores are there (csrc/auroc.hip), else the host functions -- as Evaluator chooses."""
+    scores = output.image_scores
+    if scores is None:
+        raise ValueError("image_auroc: the output carries no image_scores (tools.inference(..., image_scores='max' | 'reweighted'))")
+    targets = torch.as_tensor(output.y_true_binary_labels)
+    if scores.is_cuda:
+        return mtr.auroc_gpu(targets.to(scores.device), scores)
+    fpr, tpr, _ = mtr.compute_roc(targets.detach().cpu(), scores.detach().cpu())
+    return float(mtr.compute_auc(fpr, tpr))
+
+
 def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64) -> Tensor:
     """Image-level localisation (src/evaluator.py:268-282 of the reference): a Grad-CAM saliency of the predicted class
     for every image predicted anomalous (y_hat != 0), an all-zero map otherwise; NaNs of constant maps become 0.
@@ -636,18 +671,22 @@ def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64)
 def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = (256, 256), patch_localization: bool = True,
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
-          detector: str = 'knn', bank: str = 'reference', coreset=None):
+          detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
-    category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank` and `coreset` as in `inference`."""
+    category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores` and
+    `neighbours` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns."""
     _check_detector(detector)
     _check_bank(bank)
     _check_coreset(coreset, detector)
+    _check_image_scores(image_scores, neighbours, patch_localization, detector)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
-    rows = {}
+    rows, image_rows = {}, {}
+    score_kw = {} if image_scores is None else {"image_scores": image_scores, "neighbours": neighbours}
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
@@ -657,7 +696,9 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
                          batch_size=batch_size, projection_training_params=projection_training_params,
                          fine_tune_params=fine_tune_params, trainer_kwargs=trainer_kwargs)
             out = inference(sub_out + 'best_model.ckpt', data, subject, mvtec_inference=True,
-                            patch_localization=patch_localization, detector=detector, bank=bank, coreset=coreset)
+                            patch_localization=patch_localization, detector=detector, bank=bank, coreset=coreset, **score_kw)
+        if image_scores is not None:
+            image_rows[subject] = image_auroc(out)
         if patch_localization:
             out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False)      # stays on the device: the Evaluator's GPU metrics
         ev = Evaluator(evaluation_metrics=[m for m in metrics if (m != 'f1-score') == patch_localization or m == 'auroc'])
@@ -668,6 +709,9 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         parts = [None] * world
         dist.all_gather_object(parts, rows)
         rows = {k: v for part in parts for k, v in part.items()}
+        if image_scores is not None:
+            dist.all_gather_object(parts, image_rows)
+            image_rows = {k: v for part in parts for k, v in part.items()}
     cols = sorted({k for r in rows.values() for k in r})
     table = {c: [float(rows[s].get(c, float('nan'))) for s in categories] for c in cols}
     for c in cols:
@@ -680,4 +724,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
             mtr.export_dataframe(df, tables_output + 'markdown/', name + '.md', mode='markdown')
         except ImportError:
             pass
+        if image_scores is not None:
+            col = [float(image_rows[s]) for s in categories]
+            idf = mtr.metrics_to_dataframe({'image_auroc': col + [float(np.nanmean(col))]}, list(categories) + ['average'])
+            mtr.export_dataframe(idf, tables_output + 'csv/', 'patch_image_auroc.csv')
     return df
