@@ -460,7 +460,6 @@ def test_layer1_dedup_equals_patchwise(dev, seeded_sd, monkeypatch):
             for k in ("latent_space", "classifier"):
                 scale = ref[k].abs().max().item()
                 assert (got[k] - ref[k]).abs().max().item() <= 2e-6 * max(1.0, scale), k
-                assert not torch.equal(got[k], ref[k]) or True
         # stride 4 (extract_patches' own default, functional.py:77): 15 x 15 windows of a 88 x 88 image, pooled shift 2
         plan = m._eval_plan()
         x = ow.synthetic_images(1, 256, seed=13)[:, :, :88, :88].contiguous().to(dev)
