@@ -519,6 +519,19 @@ int ssad_rows_smallest_index(const float* m, int64_t Q, int R, int b, int cosine
 int ssad_rows_argmax(const float* s, int64_t Q, int P, float* val, int64_t* flat, void* stream);
 int ssad_knn_reweight(const float* xs, const float* bank_normalized, const int* mstar, const int* nbr, const float* smax, float* out,
                       int64_t Q, int D, int R, int bp, void* stream);
+/* Locally aware patch features from two stage maps of one trunk pass (csrc/patch_features.hip).  Replaces nothing in the reference,
+ * which scores 841 windows per image (models.py:211-219); this is the feature construction of PatchCore (Roth et al., CVPR 2022,
+ * section 3.1) as anomalib implements it: AvgPool2d(3, 1, 1) of every stage map, F.interpolate(mode='bilinear', align_corners=False)
+ * of the coarser one to the finer grid, channels concatenated.
+ *   fine [N][Hf][Wf][Cf], coarse [N][Hc][Wc][Cc] NHWC fp32 -> out [N * Hf * Wf][Cf + Cc], rows in (n, i, j) order, not normalised:
+ *   columns [0, Cf): 1/9 of the 3 x 3 neighbourhood sum of fine (zeros outside the map); columns [Cf, Cf + Cc): the bilinear blend of
+ *   the pooled coarse map P at y0, y1, x0, x1 with num = max((2 i + 1) Hc - Hf, 0), y0 = num div (2 Hf), y1 = min(y0 + 1, Hc - 1),
+ *   ly = (num - y0 2 Hf) / (2 Hf) (columns likewise): integer sample positions, correctly rounded weights.
+ *   Cf % 4 == 0, Cc % 4 == 0, 16-byte aligned pointers, map sides in 1 .. 32768, Wc <= 2048, any ratio of the two sizes.
+ *   rows_per_block: fine rows of one image a workgroup walks down, 0 = chosen by the library; the result does not depend on it.
+ *   No atomics, fixed summation order: the same bits on every call. */
+int ssad_local_patch_features(const float* fine, const float* coarse, float* out, int64_t N, int Hf, int Wf, int Cf, int Hc, int Wc,
+                              int Cc, int rows_per_block, void* stream);
 /* Greedy k-center (farthest-point) coreset of the kNN bank (PatchCore; csrc/coreset.hip; the reference has no coreset) over the
  * rows of p [R][d] (fp32, row-major), squared Euclidean distance sum_j (p[r][j] - p[c][j])^2 summed as a direct sum of squared
  * differences in one fixed order per row.  sel[0] = start; sel[t] = argmax_r min_{s<t} dist(r, sel[s]), ties to the smallest row;

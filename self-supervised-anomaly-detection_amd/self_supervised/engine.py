@@ -109,15 +109,31 @@ def param_version(model):
         next(model.parameters()).device,)
 
 
-def trunk_eval(plan, x, patch_dim, patch_stride, layer_outputs, pooled):
+def stage_shapes(h, w):
+    """(H, W, C) of the stage maps layer1 .. layer4 for a whole h x w image (h, w >= 64: no resize): conv 7 x 7 / 2, max-pool 3 x 3 / 2,
+    then one halving (rounded up) per later stage."""
+    half = lambda v: (v - 1) // 2 + 1
+    hs, ws, out = half(half(h)), half(half(w)), {}
+    for name, _, c, stride in BLOCKS:
+        if stride == 2:
+            hs, ws = half(hs), half(ws)
+        out[name] = (hs, ws, c)
+    return out
+
+
+def trunk_eval(plan, x, patch_dim, patch_stride, layer_outputs, pooled, maps=None):
     """x NCHW fp32 -> writes the GAP vectors of the requested stages into ``pooled`` [N][D].
+
+    maps: None, or a dict whose keys name stages (layer1 .. layer4): the pass then runs in NHWC whatever the batch and the map size are
+    (no position-major layout, no shared layer1) and leaves every named stage's output map [N][H][W][C] in the dict -- the dense
+    localisation takes its feature maps and the image-level logits from one pass.
 
     Many samples with small maps (the 841-patches-per-image scoring path: 64x64 inputs, maps 16x16 .. 2x2) run in
     the position-major layout [H][W][N][C]: a conv workgroup then owns 128 samples at one output position, reads
     contiguous rows for every tap and skips the taps that fall into the zero padding (8 % .. 56 % of the MACs)."""
     b, _, h, w = x.shape
     p, hv, wv, _, _ = ops.stem_geometry(h, w, patch_dim, patch_stride)
-    hwnc = b * p >= 128 and hv * wv <= 64 * 64
+    hwnc = maps is None and b * p >= 128 and hv * wv <= 64 * 64
     x3 = math_mode()
     if hwnc:
         conv = (lambda *a: ops.conv_fwd_hwnc(*a, x3=x3)) if x3 else ops.conv_fwd_hwnc
@@ -174,6 +190,8 @@ def trunk_eval(plan, x, patch_dim, patch_stride, layer_outputs, pooled):
         last_of_stage = (i % 2 == 1)
         if last_of_stage and name in offs:
             ops.gap_fwd(a, pooled, offs[name], hwnc)
+        if last_of_stage and maps is not None and name in maps:
+            maps[name] = a
     return pooled
 
 

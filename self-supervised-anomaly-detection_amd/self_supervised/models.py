@@ -82,6 +82,7 @@ class PeraNet(_Base):
 
         self.mvtec = False
         self.patch_level = False
+        self.dense_layers = None        # enable_dense_mode: the two stages whose maps become the patch features
         self.num_classes = num_classes
         self.lr = learning_rate
         self.num_epochs = epochs
@@ -135,6 +136,20 @@ class PeraNet(_Base):
 
     def disable_patch_level_mode(self):
         self.patch_level = False
+
+    def enable_dense_mode(self, layers=('layer2', 'layer3')):
+        """Dense feature-map localisation (opt-in; SPADE / PaDiM / PatchCore): in eval mode ``forward`` makes ONE trunk pass per image
+        and returns 'latent_space' = the locally aware patch features of the two stage maps `layers` (finer first; two of layer1 ..
+        layer3), one row per position of the finer map ([b * Hf * Wf][Cf + Cc], ops.local_patch_features), beside 'classifier' = the
+        image-level logits of the same pass ([b][num_classes]).  Exact fp32 and eval mode only."""
+        layers = tuple(layers) if isinstance(layers, (tuple, list)) else (layers,)
+        order = ('layer1', 'layer2', 'layer3')
+        if len(layers) != 2 or any(k not in order for k in layers) or order.index(layers[0]) >= order.index(layers[1]):
+            raise ValueError(f"dense mode takes two of {order}, the finer stage first, got {layers!r}")
+        self.dense_layers = layers
+
+    def disable_dense_mode(self):
+        self.dense_layers = None
 
     def enable_mvtec_inference(self) -> None:
         self.mvtec = True
@@ -213,24 +228,76 @@ class PeraNet(_Base):
             self._plan = engine.EvalPlan(self)
         return self._plan
 
-    def _samples_per_pass(self, b, p, hv, wv, pd, device=None):
+    def _samples_per_pass(self, b, p, hv, wv, pd, device=None, held=0):
         """Images per trunk pass: the configured cap, fewer than 2^31 elements in the largest activation (the stem map: 1/4 of the
         network input's pixels x 64 channels per sample; the 32 x 32 patch path fuses stem + pool: 1/16), and what the free HBM
-        holds (free = the driver's free bytes + what torch's allocator has cached but not handed out)."""
+        holds (free = the driver's free bytes + what torch's allocator has cached but not handed out).  held: floats per sample
+        that stay alive through the whole pass beside the activations (the stage maps of the dense mode)."""
         shrink = 4 if pd == 32 else 2
         act = max(1, (hv // shrink) * (wv // shrink) * 64)                       # floats of the largest activation per sample
         cap = min(self.max_samples_per_pass, self.max_elements_per_tensor // act)
         free, _ = torch.cuda.mem_get_info(device)
         free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
         live = 4 if pd == 32 else 3                                              # tensors of that size alive at once (+ 25 % for the deeper stages)
-        cap = min(cap, int(self.hbm_fraction_per_pass * free / (act * 4 * live * 1.25)))
+        cap = min(cap, int(self.hbm_fraction_per_pass * free / (act * 4 * live * 1.25 + held * 4)))
         per_pass = max(1, cap // p)
         return -(-b // -(-b // per_pass))               # equal passes (256 images: 2 x 128 rather than 155 + 101)
 
+    def _dense_geometry(self, x):
+        """((Hf, Wf, Cf), (Hc, Wc, Cc)) of the dense mode's two stage maps for the batch x; ValueError for what the mode does not
+        cover -- raised from shapes and switches alone, before anything is launched."""
+        if self.patch_level:
+            raise ValueError("dense mode and patch-level mode are two localisations: disable one of them")
+        if self.training:
+            raise ValueError("dense mode is an inference mode: call model.eval() first")
+        if engine.math_mode():
+            raise ValueError("dense mode is exact fp32 only: unset SSAD_MATH (or set it to f32)")
+        h, w = int(x.shape[-2]), int(x.shape[-1])
+        if h < 64 or w < 64:
+            raise ValueError(f"dense mode needs images of at least 64 x 64 pixels, got {h} x {w} (the reference's resize of smaller "
+                             "inputs belongs to the window modes)")
+        shapes = engine.stage_shapes(h, w)
+        fine, coarse = shapes[self.dense_layers[0]], shapes[self.dense_layers[1]]
+        if fine[0] != fine[1]:
+            raise ValueError(f"dense mode needs a square {self.dense_layers[0]} map (the detectors reshape scores to dim x dim), "
+                             f"got {fine[0]} x {fine[1]} for images of {h} x {w}")
+        return fine, coarse
+
+    def _forward_dense(self, x, fine, coarse):
+        b, _, h, w = x.shape
+        p, d = fine[0] * fine[1], fine[2] + coarse[2]
+        self.batch, self.num_patches = b, p
+        plan = self._eval_plan()
+        pooled = torch.empty((b, self.concatenator[0].in_features), device=x.device, dtype=torch.float32)
+        rows = torch.empty((b * p, d), device=x.device, dtype=torch.float32)        # allocated before the free HBM is read below
+        held = p * fine[2] + coarse[0] * coarse[1] * coarse[2]
+        per_pass = self._samples_per_pass(b, 1, h, w, 0, x.device, held)
+        i0 = 0
+        while i0 < b:
+            i1 = min(b, i0 + per_pass)
+            try:
+                maps = dict.fromkeys(self.dense_layers)
+                engine.trunk_eval(plan, x[i0:i1], 0, 0, self.layer_outputs, pooled[i0:i1], maps)
+                ops.local_patch_features(maps[self.dense_layers[0]], maps[self.dense_layers[1]], rows[i0 * p:i1 * p])
+            except torch.cuda.OutOfMemoryError:
+                if per_pass == 1:
+                    raise
+                maps = None
+                torch.cuda.empty_cache()
+                per_pass = max(1, per_pass // 2)
+                continue
+            self.last_pass_samples = (i1 - i0) if i0 == 0 else self.last_pass_samples
+            i0 = i1
+        logits, _ = engine.head_eval(plan, pooled)
+        return {'classifier': logits, 'latent_space': rows}
+
     def forward(self, x: Tensor) -> dict:
+        dense = self._dense_geometry(x) if self.dense_layers is not None else None
         if not x.is_cuda:
             raise RuntimeError("PeraNet.forward runs on the MI355X HIP kernels only: move the batch to the GPU")
         x = x.contiguous().float()
+        if dense is not None:
+            return self._forward_dense(x, *dense)
         if self.training and torch.is_grad_enabled():
             from . import training
             return training.forward_train(self, x)

@@ -827,6 +827,34 @@ def knn_reweight(xs, bank_n, mstar, nbr, smax):
     return out
 
 
+def bilinear_taps(nf, nc):
+    """The sample positions csrc/patch_features.hip uses to resample nc positions to nf (F.interpolate's align_corners=False rule in
+    integer arithmetic): per destination index i, num = max((2 i + 1) nc - nf, 0), a = num // (2 nf), b = min(a + 1, nc - 1) and the
+    weight of b as the exact fraction (num - a 2 nf, 2 nf).  Returns (a, b, weight numerators, denominator) as Python ints."""
+    num = [max((2 * i + 1) * nc - nf, 0) for i in range(nf)]
+    a = [v // (2 * nf) for v in num]
+    return a, [min(v + 1, nc - 1) for v in a], [v - u * 2 * nf for v, u in zip(num, a)], 2 * nf
+
+
+def local_patch_features(fine, coarse, out=None, rows_per_block=0):
+    """Locally aware patch features (PatchCore §3.1 / anomalib; csrc/patch_features.hip): fine [N][Hf][Wf][Cf], coarse [N][Hc][Wc][Cc]
+    NHWC -> [N * Hf * Wf][Cf + Cc]: the 3 x 3 average of `fine` beside the 3 x 3 average of `coarse` resampled bilinearly
+    (align_corners=False) to the fine grid, rows in (n, i, j) order, not normalised.  out: a contiguous buffer of that shape to fill.
+    rows_per_block: the kernel's row band (0: automatic); the result does not depend on it."""
+    n, hf, wf, cf = fine.shape
+    n2, hc, wc, cc = coarse.shape
+    if n2 != n:
+        raise _hip.HipExtensionError(f"local_patch_features: {n} fine maps but {n2} coarse maps")
+    if out is None:
+        out = _new((n * hf * wf, cf + cc), fine)
+    elif tuple(out.shape) != (n * hf * wf, cf + cc):
+        raise _hip.HipExtensionError(f"local_patch_features: out is {tuple(out.shape)}, expected {(n * hf * wf, cf + cc)}")
+    _run("local_patch_features", 0.0, 4.0 * (fine.numel() + coarse.numel() + out.numel()),
+         lambda: _hip.lib().ssad_local_patch_features(_hip.ptr(fine), _hip.ptr(coarse), _hip.ptr(out), n, hf, wf, cf, hc, wc, cc,
+                                                      rows_per_block, _hip.stream()))
+    return out
+
+
 def gaussian_fit_stats(x, normalize=True):
     """x [N][D] fp32 -> (mean [D], scatter [D][D], m4 [1]) fp64 of its rows (L2-normalised first when `normalize`): the centred
     sufficient statistics of a Ledoit-Wolf Gaussian fit (csrc/gde.hip), deterministic."""

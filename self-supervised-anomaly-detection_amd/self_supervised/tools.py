@@ -282,13 +282,13 @@ def _predict_mvtec_streamed(model: PeraNet, dataset, device, indices, group: int
     pending = None                                       # (a, b, orig_dev, x_dev, event) of the group whose results are still on the device
 
     def drain(item):
-        a, b, o_dev, x_dev, ev, p = item
+        a, b, o_dev, x_dev, ev, p, q = item
         with torch.cuda.stream(side):
             side.wait_event(ev)
             orig[a:b].copy_(o_dev)
             xnorm[a:b].copy_(x_dev)
             emb_host[a * p:b * p].copy_(emb_dev[a * p:b * p])
-            logits_host[a * p:b * p].copy_(logits_dev[a * p:b * p])
+            logits_host[a * q:b * q].copy_(logits_dev[a * q:b * q])
         for t in (o_dev, x_dev):
             t.record_stream(side)
     # groups of equal size, about `group` images each (97 images = 96 + the bank image: three forwards of 33 / 32 / 32, not 32 / 32 / 32
@@ -307,31 +307,32 @@ def _predict_mvtec_streamed(model: PeraNet, dataset, device, indices, group: int
                 _hip.check(lib.ssad_u8hwc_to_f32chw_norm(img_dev.data_ptr(), o_dev.data_ptr(), x_dev.data_ptr(), b - a, h_img, w_img,
                                                          mean, std, _hip.stream()))
                 pred = model(x_dev)
-                p = pred['latent_space'].shape[0] // (b - a)
+                # rows per image: the embeddings' and the logits' (the dense mode has one row of logits per image beside its patch rows)
+                p, q = pred['latent_space'].shape[0] // (b - a), pred['classifier'].shape[0] // (b - a)
                 if emb_dev is None:
                     d, c = pred['latent_space'].shape[1], pred['classifier'].shape[1]
                     emb_dev = torch.empty((n * p, d), device=device, dtype=torch.float32)
-                    logits_dev = torch.empty((n * p, c), device=device, dtype=torch.float32)
-                    emb_host, logits_host = torch.empty((n * p, d)), torch.empty((n * p, c))
+                    logits_dev = torch.empty((n * q, c), device=device, dtype=torch.float32)
+                    emb_host, logits_host = torch.empty((n * p, d)), torch.empty((n * q, c))
                 emb_dev[a * p:b * p].copy_(pred['latent_space'])
-                logits_dev[a * p:b * p].copy_(pred['classifier'])
+                logits_dev[a * q:b * q].copy_(pred['classifier'])
                 ev = torch.cuda.Event()
                 ev.record(main)
                 if pending is not None:
                     drain(pending)                          # the previous group's results travel while this group computes
-                pending = (a, b, o_dev, x_dev, ev, p)
+                pending = (a, b, o_dev, x_dev, ev, p, q)
             drain(pending)
     except BaseException:
         pre.close(cancel=True)                           # a failing predict must not leave decode threads running until exit
         raise
     pre.close()
     side.synchronize()
-    p = emb_dev.shape[0] // n
+    p, q = emb_dev.shape[0] // n, logits_dev.shape[0] // n
     if ne:
         # the images in front are not part of the dataset's output: their embeddings stay on the device for the caller
         out.extra_embeddings = emb_dev[:ne * p]
         orig, xnorm, gt8 = orig[ne:], xnorm[ne:], gt8[ne:]
-        emb_host, logits_host, emb_dev = emb_host[ne * p:], logits_host[ne * p:], emb_dev[ne * p:]
+        emb_host, logits_host, emb_dev = emb_host[ne * p:], logits_host[ne * q:], emb_dev[ne * p:]
     gts = torch.from_numpy(gt8).float().div_(255.0).unsqueeze(1)
     out.original_data, out.tensor_data, out.ground_truths = orig, xnorm, gts
     out.raw_predictions, out.embedding_vectors = logits_host, emb_host
@@ -392,6 +393,19 @@ def _check_image_scores(image_scores, neighbours, patch_localization, detector):
     return image_scores
 
 
+LOCALIZATIONS = ('patches', 'dense')
+
+
+def _check_localization(localization, patch_localization):
+    """'patches' = the reference's 841 windows per image; 'dense' = one trunk pass per image and the locally aware patch features of
+    two stage maps (PeraNet.enable_dense_mode), a patch-level localisation like the first."""
+    if localization not in LOCALIZATIONS:
+        raise ValueError(f"localization must be one of {LOCALIZATIONS}, got {localization!r}")
+    if localization == 'dense' and not patch_localization:
+        raise ValueError("localization='dense' needs patch_localization=True: it is a patch-level localisation")
+    return localization
+
+
 def _print_coreset(detector):
     counts = getattr(detector, "coreset_counts", None)
     if counts is not None:
@@ -426,7 +440,8 @@ def _train_bank_rows(per_image, n_total, device):
 
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
-              coreset=None, image_scores: str = None, neighbours: int = 9) -> ModelOutputsContainer:
+              coreset=None, image_scores: str = None, neighbours: int = 9,
+              localization: str = 'patches') -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -437,8 +452,13 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     `image_scores`: None (default) = maps only, as the reference; 'max' / 'reweighted' = the container also carries
     `image_scores` [n_images] (test-set file order): the largest raw patch score of every image, for 'reweighted' weighted by the
     `neighbours` (2..32, default 9) bank rows around its nearest bank row (AnomalyDetector.image_scores; PatchCore eq. 6-7).  Needs
-    patch_localization=True and detector='knn'; the maps are unchanged."""
+    patch_localization=True and detector='knn'; the maps are unchanged.
+    `localization`: how patch_localization=True gets its rows.  'patches' (default) = the reference's 32 x 32 windows at stride 8, one
+    trunk pass per window (29 x 29 maps for 256 x 256 images); 'dense' = one trunk pass per image, rows = the locally aware patch
+    features of the layer2 and layer3 maps (PeraNet.enable_dense_mode: 32 x 32 maps, 384 columns); everything after the rows is the
+    same code."""
     scorer = _check_detector(detector)
+    _check_localization(localization, patch_localization)
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, scorer)
     _check_image_scores(image_scores, neighbours, patch_localization, scorer)
@@ -491,7 +511,9 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         model = PeraNet.load_from_checkpoint(model_input_dir)
         _mark("checkpoint")
         model.eval()
-        if patch_localization:
+        if patch_localization and localization == 'dense':
+            model.enable_dense_mode()
+        elif patch_localization:
             model.enable_patch_level_mode()
         tester = Trainer(accelerator='auto', devices=1)
     except BaseException:
@@ -671,22 +693,26 @@ def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64)
 def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = (256, 256), patch_localization: bool = True,
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
-          detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9):
+          detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
+          localization: str = 'patches'):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
-    category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores` and
-    `neighbours` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
+    `neighbours` and `localization` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns."""
     _check_detector(detector)
     _check_bank(bank)
     _check_coreset(coreset, detector)
     _check_image_scores(image_scores, neighbours, patch_localization, detector)
+    _check_localization(localization, patch_localization)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}
     score_kw = {} if image_scores is None else {"image_scores": image_scores, "neighbours": neighbours}
+    if localization != 'patches':
+        score_kw["localization"] = localization
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
