@@ -553,6 +553,21 @@ int ssad_coreset_greedy(const float* p, int64_t R, int d, int m, int64_t start, 
 int ssad_gaussian_fit_stats(const float* x, int64_t N, int D, int normalize, double* mean, double* scatter, double* m4, void* stream);
 int ssad_mahalanobis_fused(const float* x, const float* mu_hi, const float* mu_lo, const float* w, float* out, int64_t N, int D,
                            int normalize, void* stream);
+/* Per-position Gaussian detector (PaDiM, Defard et al. ICPR 2020; csrc/padim.hip; the reference has no such scorer) on dense rows
+ * x [n_img * P][D], row n P + p = position p of image n; sel [d] int32 on the device picks d of the D columns (every entry in
+ * [0, D): the caller checks it).
+ * ssad_position_gaussian_fit_stats: per position, in fp64, mean[P][d] and scatter[P][d][d] = sum_n c c^T of the centred selected
+ *   columns; images summed in ascending order, each 64 x 64 tile of the lower triangle mirrored exactly, no atomics: the same bits on
+ *   every call.  n_img >= 2.
+ * ssad_position_mahalanobis: out[n P + p] = ||W_p (x_sel - mu_p)||_2 in one kernel on the fp32 matrix cores, mu_p = mu_hi[p] +
+ *   mu_lo[p] ([P][d] float pairs: (x - mu_hi) - mu_lo), W_p = w[p] [d][d] lower triangular (whatever its upper triangle holds is never
+ *   used).  A workgroup owns one position and 128 images and runs over all of W_p: a score does not depend on n_img or on where its
+ *   image sits in the launch.  d <= 1024, 512 (P + 1) D <= 2^31, sel / mu_hi / mu_lo / w 16-byte aligned.
+ * Both: d % 32 == 0, 32 <= d <= D, D % 4 == 0, P >= 1, n_img >= 1; anything else returns the argument error without a launch. */
+int ssad_position_gaussian_fit_stats(const float* x, const int* sel, int n_img, int64_t P, int D, int d, double* mean, double* scatter,
+                                     void* stream);
+int ssad_position_mahalanobis(const float* x, const int* sel, const float* mu_hi, const float* mu_lo, const float* w, float* out,
+                              int n_img, int64_t P, int D, int d, void* stream);
 /* HOST function (no GPU work): per-channel integer sums of the window [top, top + h) x [left, left + w) of the NEAREST affine
  * transform of an H x W x 3 uint8 image (fix: the six 16.16 coefficients of ssad_aug_params.aff_fix; NULL: the image itself),
  * zero outside the image.  The sampler's colour-similarity test (datasets.py:300-312) needs this mean between two random

@@ -10,6 +10,10 @@ the GPU (csrc/gde.hip); the one-off D x D shrinkage, Cholesky factor and its tri
 ``normalize=True`` (the default) scores L2-normalised embeddings: the view of the embedding the cosine detector has, and what the
 common PyTorch re-implementations of CutPaste feed their GDE.  The rows are normalised on the GPU bit-identically to
 ``ops.l2_normalize_rows``.
+
+``PositionGaussianDetector`` (below) is the per-position form for dense localisation (PaDiM): one Gaussian per map position over a
+random choice of columns, fitted over the training images (csrc/padim.hip); its yardstick is numpy.cov + eps I and scipy's
+mahalanobis in float64.
 """
 import numpy as np
 import torch
@@ -150,4 +154,174 @@ class GaussianDensityDetector:
         det = cls(patch_level=patch_level, batch=batch, num_patches=num_patches, normalize=state["normalize"])
         det.mu_hi, det.mu_lo, det.w = (cls._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
         det.shrinkage = state["shrinkage"]
+        return det
+
+
+# ------------------------------------------------------------------------------------------------ per-position Gaussian (PaDiM)
+
+def position_channels(D: int, d: int, seed: int = 0):
+    """The `d` of `D` columns the per-position Gaussian keeps (PaDiM's random dimension reduction): ``randperm(D)[:d]`` on a CPU
+    torch.Generator of its own seeded with `seed`, sorted ascending, int64; d == D = every column, no draw.  Never draws from the
+    global torch, numpy or `random` generators (as models.coreset_projection).  ValueError unless d % 32 == 0 and 32 <= d <= D."""
+    if isinstance(d, (bool, np.bool_)) or not isinstance(d, (int, np.integer)) or d % 32 or not 32 <= d <= D:
+        raise ValueError(f"channels must be a multiple of 32 in 32..{int(D)} (the rows' width), got {d!r}")
+    if d == D:
+        return torch.arange(D, dtype=torch.int64)
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    return torch.randperm(int(D), generator=g)[:int(d)].sort().values
+
+
+def position_gaussian_factor(mean, scatter, n, eps=0.01, chunk=64, dtype=np.float32):
+    """The per-position Gaussians in the form the scoring kernel takes, from the statistics of ``ops.position_gaussian_fit_stats``:
+    Sigma_p = scatter_p / (n - 1) + eps I (numpy.cov plus PaDiM's regulariser), C_p = cholesky(Sigma_p) (lower), W_p = C_p^-1
+    (batched triangular solve), all in float64 on the host, `chunk` positions at a time.  Returns (mu_hi [P][d], mu_lo [P][d],
+    W [P][d][d]) float32: the mean as the pair fp32(mean), fp32(mean - mu_hi) of ``ledoit_wolf_factor``, W lower triangular with
+    exact zeros above the diagonal (dtype=np.float64: W before that rounding, for checks).  ValueError for n < 2 or eps <= 0 (with eps > 0 every Sigma_p is positive definite)."""
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    scatter = np.ascontiguousarray(scatter, dtype=np.float64)
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"a per-position Gaussian needs at least 2 fit images, got {n}")
+    if not eps > 0:
+        raise ValueError(f"eps must be positive (it keeps every covariance positive definite), got {eps!r}")
+    P, d = mean.shape
+    if scatter.shape != (P, d, d):
+        raise ValueError(f"scatter is {scatter.shape}, expected {(P, d, d)}")
+    w = np.empty((P, d, d), dtype=dtype)
+    eye = torch.eye(d, dtype=torch.float64)
+    for a in range(0, P, chunk):
+        sigma = scatter[a:a + chunk] / (n - 1)
+        sigma[:, np.arange(d), np.arange(d)] += eps
+        try:
+            c = np.linalg.cholesky(sigma)
+        except np.linalg.LinAlgError as e:      # (not reachable with finite statistics and eps > 0)
+            raise ValueError(f"a covariance of positions {a}..{min(P, a + chunk) - 1} is not positive definite") from e
+        wc = torch.linalg.solve_triangular(torch.from_numpy(c), eye.expand(c.shape[0], d, d), upper=False)
+        w[a:a + chunk] = np.tril(wc.numpy())
+    mu_hi = mean.astype(np.float32)
+    mu_lo = (mean - mu_hi.astype(np.float64)).astype(np.float32)
+    return mu_hi, mu_lo, w
+
+
+class PositionGaussianDetector:
+    """Opt-in third scorer (PaDiM, Defard et al., ICPR 2020, as anomalib implements it) with ``GaussianDensityDetector``'s call
+    surface, for rows that are whole images of `num_patches` positions in (image, position) order (the dense rows of
+    ``PeraNet.enable_dense_mode``): one Gaussian per position over `channels` randomly chosen columns (``position_channels``),
+    fitted over the images, the Mahalanobis distance to it as the pixel score.  Rows are not L2-normalised.
+
+    ``fit`` draws the 70/30 split over images (models.split_rows; `groups` given or implied by the row order), fits on the 70 % and
+    sets ``threshold`` to the largest score of the held-out images.  Patch level only, at least 2 fit images."""
+
+    def __init__(self, patch_level: bool = True, batch: int = None, num_patches: int = None, channels: int = 96, eps: float = 0.01,
+                 seed: int = 0) -> None:
+        if not patch_level or not num_patches:
+            raise ValueError("PositionGaussianDetector is a patch-level detector: patch_level=True and num_patches (positions per "
+                             "image) are required")
+        if isinstance(channels, (bool, np.bool_)) or not isinstance(channels, (int, np.integer)) or channels % 32 or channels < 32:
+            raise ValueError(f"channels must be a multiple of 32, at least 32, got {channels!r}")
+        if not eps > 0:
+            raise ValueError(f"eps must be positive, got {eps!r}")
+        self.patch_level = True
+        self.batch = batch
+        self.num_patches = int(num_patches)
+        self.dim = int(np.sqrt(num_patches))
+        self.channels, self.eps, self.seed = int(channels), float(eps), int(seed)
+        self.sel = self.mu_hi = self.mu_lo = self.w = None
+        self._sel_dev = None
+        self.threshold = None
+
+    @staticmethod
+    def _dev(t):
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if not t.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError("PositionGaussianDetector needs the MI355X HIP kernels (no CPU fallback)")
+            t = t.cuda()
+        return t.contiguous()
+
+    @staticmethod
+    def fit_images(n_img: int, split: bool = True) -> int:
+        """Images a fit on n_img images uses (the train part of the 70/30 split); ValueError when fewer than 2."""
+        m = n_img - int(np.ceil(0.3 * n_img)) if split else n_img
+        if m < 2:
+            raise ValueError(f"PositionGaussianDetector needs at least 2 fit images, got {m} (from {n_img} images"
+                             f"{', 70/30 split' if split else ''}): one image gives no covariance")
+        return m
+
+    def _images(self, rows: int) -> int:
+        if rows == 0 or rows % self.num_patches:
+            raise ValueError(f"{rows} rows are not whole images of {self.num_patches} positions")
+        return rows // self.num_patches
+
+    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
+        """groups: image index per row (default: implied by the row order, `num_patches` rows per image)."""
+        from .models import _take, split_rows
+        emb = torch.as_tensor(embeddings)
+        n_img = self._images(int(emb.shape[0]))
+        position_channels(int(emb.shape[1]), self.channels, self.seed)
+        self.fit_images(n_img, split)
+        if split:
+            if groups is None:
+                groups = torch.arange(n_img).repeat_interleave(self.num_patches)
+            else:
+                g = torch.as_tensor(groups).cpu().reshape(-1).long()
+                if g.numel() != emb.shape[0] or not torch.equal(torch.bincount(g, minlength=n_img),
+                                                                torch.full((n_img,), self.num_patches)):
+                    raise ValueError(f"groups must give every one of the {n_img} images {self.num_patches} rows")
+            train_idx, val_idx = split_rows(int(emb.shape[0]), groups, 0.3)
+            train, val = _take(emb, train_idx), _take(emb, val_idx)
+        else:
+            train, val = emb, emb
+        self.fit_bank(train)
+        self.threshold = torch.max(self._scores(self._dev(val))).item()
+
+    def fit_bank(self, bank: Tensor) -> None:
+        bank = torch.as_tensor(bank)
+        n_img = self._images(int(bank.shape[0]))
+        sel = position_channels(int(bank.shape[1]), self.channels, self.seed)
+        self.fit_images(n_img, split=False)
+        x = self._dev(bank)
+        sel_dev = ops.position_sel(sel, x.shape[1], x.device)
+        mean, scatter = ops.position_gaussian_fit_stats(x, sel, n_img, self.num_patches, sel_dev=sel_dev)
+        mu_hi, mu_lo, w = position_gaussian_factor(mean.cpu().numpy(), scatter.cpu().numpy(), n_img, self.eps)
+        self.sel, self._sel_dev = sel, sel_dev
+        self.mu_hi, self.mu_lo, self.w = (torch.from_numpy(a).to(x.device) for a in (mu_hi, mu_lo, w))
+
+    def _scores(self, x):
+        if self.w is None:
+            raise ValueError("PositionGaussianDetector: not fitted (fit or fit_bank first)")
+        n_img = self._images(int(x.shape[0]))
+        if int(self.sel.max()) >= x.shape[1]:
+            raise ValueError(f"the rows have {x.shape[1]} columns, the fitted selection reaches column {int(self.sel.max())}")
+        return ops.position_mahalanobis(x, self.sel, self.mu_hi, self.mu_lo, self.w, n_img, self.num_patches, sel_dev=self._sel_dev)
+
+    def predict(self, x: Tensor) -> Tensor:
+        s = self._scores(self._dev(x))
+        return torch.reshape(s, (s.shape[0] // self.num_patches if self.batch is None else self.batch, 1, self.dim, self.dim))
+
+    def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = None, scores: Tensor = None) -> Tensor:
+        """PaDiM's image score: the largest patch score of every image (ops.rows_argmax).  x [batch * P][D]; `scores`: the map
+        predict returned, when the caller has it already.  'reweighted' needs a nearest bank row, which a Gaussian has not;
+        `neighbours` belongs to that mode and is accepted for AnomalyDetector's call surface only."""
+        if mode != 'max':
+            raise ValueError(f"PositionGaussianDetector.image_scores: mode must be 'max' (a Gaussian patch score has no nearest bank "
+                             f"row to reweight with), got {mode!r}")
+        x = self._dev(x)
+        n_img = self._images(int(x.shape[0]))
+        s = self._scores(x) if scores is None else self._dev(scores)
+        smax, _ = ops.rows_argmax(s.reshape(n_img, self.num_patches))
+        return smax
+
+    def state(self) -> dict:
+        """What another rank needs to score (host tensors, picklable); the threshold travels beside it."""
+        return {"sel": self.sel.cpu(), "mu_hi": self.mu_hi.cpu(), "mu_lo": self.mu_lo.cpu(), "w": self.w.cpu(), "eps": self.eps,
+                "channels": self.channels, "seed": self.seed}
+
+    @classmethod
+    def from_state(cls, state: dict, patch_level: bool = True, batch: int = None, num_patches: int = None):
+        det = cls(patch_level=patch_level, batch=batch, num_patches=num_patches, channels=state["channels"], eps=state["eps"],
+                  seed=state.get("seed", 0))
+        det.mu_hi, det.mu_lo, det.w = (cls._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
+        det.sel = torch.as_tensor(state["sel"]).cpu().long()
+        det._sel_dev = ops.position_sel(det.sel, int(det.sel.max()) + 1, det.mu_hi.device)
         return det

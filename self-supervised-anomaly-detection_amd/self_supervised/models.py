@@ -593,3 +593,4 @@ class AnomalyDetector:
 
 
 from .density import GaussianDensityDetector  # noqa: E402,F401  (opt-in second scorer: Ledoit-Wolf Gaussian, Mahalanobis distance)
+from .density import PositionGaussianDetector  # noqa: E402,F401  (opt-in third scorer: PaDiM, one Gaussian per map position)

@@ -880,6 +880,62 @@ def mahalanobis_fused(x, mu_hi, mu_lo, w, normalize=True):
     return out
 
 
+def position_sel(sel, D, device):
+    """The channel selection of the per-position Gaussian, checked where it lives (on the host): `sel` [d] integers, every entry in
+    [0, D) -> an int32 tensor on `device`.  HipExtensionError otherwise, before anything is launched."""
+    s = torch.as_tensor(sel).detach().cpu().reshape(-1)
+    if s.dtype not in (torch.int32, torch.int64) or s.numel() == 0:
+        raise _hip.HipExtensionError(f"position_sel: sel must be a non-empty int32 / int64 vector, got {s.dtype} x {s.numel()}")
+    if int(s.min()) < 0 or int(s.max()) >= int(D):
+        raise _hip.HipExtensionError(f"position_sel: sel has an entry outside [0, {int(D)}) (min {int(s.min())}, max {int(s.max())})")
+    return s.to(torch.int32).to(device).contiguous()
+
+
+def _position_shape(x, n_img, P):
+    rows, D = x.shape
+    if n_img < 1 or P < 1 or rows != n_img * P:
+        raise _hip.HipExtensionError(f"{rows} rows are not {n_img} images of {P} positions")
+    return D
+
+
+def position_gaussian_fit_stats(x, sel, n_img, P, sel_dev=None):
+    """x [n_img * P][D] fp32 (row n P + p) -> (mean [P][d], scatter [P][d][d]) fp64 of the columns `sel` per position p over the
+    images (csrc/padim.hip), deterministic.  sel: host integers, checked here; sel_dev: its device copy from position_sel, when the
+    caller keeps one."""
+    D = _position_shape(x, n_img, P)
+    sd = position_sel(sel, D, x.device) if sel_dev is None else sel_dev
+    d = int(sd.numel())
+    f64 = torch.float64
+    mean = torch.empty((P, d), device=x.device, dtype=f64)
+    scatter = torch.empty((P, d, d), device=x.device, dtype=f64)
+    t = (d + 63) // 64
+    _run("position_gaussian_fit_stats", 2.0 * n_img * P * d * (d + 1) / 2 + 2.0 * n_img * P * d,
+         4.0 * n_img * P * d * (1 + t) + 8.0 * P * d * (d + 1),
+         lambda: _hip.lib().ssad_position_gaussian_fit_stats(_hip.ptr(x), _hip.ptr(sd, dtype=torch.int32), n_img, P, D, d,
+                                                             _hip.ptr(mean, dtype=f64), _hip.ptr(scatter, dtype=f64), _hip.stream()))
+    return mean, scatter
+
+
+def position_mahalanobis(x, sel, mu_hi, mu_lo, w, n_img, P, sel_dev=None, out=None):
+    """x [n_img * P][D] fp32 -> [n_img * P] ||W_p (x[n P + p][sel] - mu_p)||_2 with mu = mu_hi + mu_lo ([P][d] fp32 pairs) and
+    W [P][d][d] lower triangular, one kernel (csrc/padim.hip).  FLOPs: the dense 2 n P d^2 (the kernel skips W's zero blocks); bytes:
+    every row of x (d random columns of D touch all its 128-byte lines) plus W and the means once."""
+    D = _position_shape(x, n_img, P)
+    sd = position_sel(sel, D, x.device) if sel_dev is None else sel_dev
+    d = int(sd.numel())
+    if tuple(mu_hi.shape) != (P, d) or tuple(mu_lo.shape) != (P, d) or tuple(w.shape) != (P, d, d):
+        raise _hip.HipExtensionError(f"position_mahalanobis: mu_hi {tuple(mu_hi.shape)}, mu_lo {tuple(mu_lo.shape)}, w "
+                                     f"{tuple(w.shape)} do not match P = {P}, d = {d}")
+    if out is None:
+        out = _new((n_img * P,), x)
+    elif tuple(out.shape) != (n_img * P,):
+        raise _hip.HipExtensionError(f"position_mahalanobis: out is {tuple(out.shape)}, expected {(n_img * P,)}")
+    _run("position_mahalanobis", 2.0 * n_img * P * d * d, 4.0 * (x.numel() + w.numel() + 2 * P * d + n_img * P),
+         lambda: _hip.lib().ssad_position_mahalanobis(_hip.ptr(x), _hip.ptr(sd, dtype=torch.int32), _hip.ptr(mu_hi), _hip.ptr(mu_lo),
+                                                      _hip.ptr(w), _hip.ptr(out), n_img, P, D, d, _hip.stream()))
+    return out
+
+
 def blur_relu_bilinear(maps, ksize=7, target=256):
     n, c, h, w = maps.shape
     out = _new((n, c, target, target), maps)

@@ -17,7 +17,8 @@ from . import metrics as mtr
 from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
-from .models import AnomalyDetector, GaussianDensityDetector, PeraNet, check_coreset, check_image_scores
+from .models import (AnomalyDetector, GaussianDensityDetector, PeraNet, PositionGaussianDetector, check_coreset,
+                     check_image_scores)
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -354,7 +355,7 @@ def _mark(name):
         TIMELINE.append((name, time.perf_counter()))
 
 
-DETECTORS = ('knn', 'gde')
+DETECTORS = ('knn', 'gde', 'padim')
 
 
 def _check_detector(detector):
@@ -379,6 +380,8 @@ def _check_coreset(coreset, detector):
     would bias its covariance."""
     if coreset is not None and detector == 'gde':
         raise ValueError("coreset applies to detector='knn' only: the Gaussian density detector is fitted on every row")
+    if coreset is not None and detector == 'padim':
+        raise ValueError("coreset applies to detector='knn' only: the per-position Gaussians are fitted on every image")
     return check_coreset(coreset)
 
 
@@ -390,6 +393,9 @@ def _check_image_scores(image_scores, neighbours, patch_localization, detector):
         raise ValueError("image_scores needs patch_localization=True: the image level scores images already")
     if image_scores is not None and detector == 'gde':
         raise ValueError("image_scores applies to detector='knn' only: a Gaussian patch score has no nearest bank row")
+    if image_scores == 'reweighted' and detector == 'padim':
+        raise ValueError("image_scores='reweighted' applies to detector='knn' only: a Gaussian patch score has no nearest bank row "
+                         "(detector='padim' takes image_scores='max', PaDiM's image score)")
     return image_scores
 
 
@@ -404,6 +410,32 @@ def _check_localization(localization, patch_localization):
     if localization == 'dense' and not patch_localization:
         raise ValueError("localization='dense' needs patch_localization=True: it is a patch-level localisation")
     return localization
+
+
+PADIM_OPTIONS = ('channels', 'eps', 'seed')
+
+
+def _check_padim(detector, patch_localization, localization, bank, detector_options):
+    """detector='padim' (PositionGaussianDetector) fits one Gaussian per map position over the training images: it needs
+    positions that mean the same place in every image (patch_localization=True, localization='dense': one trunk pass per image) and
+    more than one training image (bank='train': the reference's bank is ONE image, which gives no covariance).
+    `detector_options` (channels / eps / seed of the detector) belongs to 'padim' alone."""
+    if detector_options is not None:
+        if detector != 'padim':
+            raise ValueError(f"detector_options applies to detector='padim' only, got detector={detector!r}")
+        if not isinstance(detector_options, dict) or any(k not in PADIM_OPTIONS for k in detector_options):
+            raise ValueError(f"detector_options must be a dict with keys among {PADIM_OPTIONS}, got {detector_options!r}")
+    if detector != 'padim':
+        return {}
+    if not patch_localization:
+        raise ValueError("detector='padim' needs patch_localization=True: it scores map positions")
+    if localization != 'dense':
+        raise ValueError("detector='padim' needs localization='dense': its positions come from one trunk pass per image")
+    if bank != 'train':
+        raise ValueError("detector='padim' needs bank='train': one training image cannot give a covariance")
+    opts = dict(detector_options or {})
+    PositionGaussianDetector(num_patches=1, **opts)         # the detector's own argument checks, before any file is read
+    return opts
 
 
 def _print_coreset(detector):
@@ -441,7 +473,7 @@ def _train_bank_rows(per_image, n_total, device):
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
               coreset=None, image_scores: str = None, neighbours: int = 9,
-              localization: str = 'patches') -> ModelOutputsContainer:
+              localization: str = 'patches', detector_options: dict = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -456,12 +488,17 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     `localization`: how patch_localization=True gets its rows.  'patches' (default) = the reference's 32 x 32 windows at stride 8, one
     trunk pass per window (29 x 29 maps for 256 x 256 images); 'dense' = one trunk pass per image, rows = the locally aware patch
     features of the layer2 and layer3 maps (PeraNet.enable_dense_mode: 32 x 32 maps, 384 columns); everything after the rows is the
-    same code."""
+    same code.
+    detector='padim' = one Gaussian per map position (PositionGaussianDetector: PaDiM; the Mahalanobis distance to the position's
+    Gaussian over `channels` randomly chosen columns); needs patch_localization=True, localization='dense' and bank='train'; takes
+    image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed'} of that detector
+    ('padim' only)."""
     scorer = _check_detector(detector)
     _check_localization(localization, patch_localization)
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, scorer)
     _check_image_scores(image_scores, neighbours, patch_localization, scorer)
+    padim_kw = _check_padim(scorer, patch_localization, localization, bank, detector_options)
     whole = bank == 'train'
     del TIMELINE[:]
     print('>>> initializing inference')
@@ -548,8 +585,8 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         n_pred = len(predictions)
     print('>>> anomaly detection phase')
     groups = None
-    kind = GaussianDensityDetector if scorer == 'gde' else AnomalyDetector
-    det_kw = {} if coreset is None else {"coreset": coreset}
+    kind = {'gde': GaussianDensityDetector, 'padim': PositionGaussianDetector}.get(scorer, AnomalyDetector)
+    det_kw = dict(padim_kw) if scorer == 'padim' else ({} if coreset is None else {"coreset": coreset})
     if patch_localization:
         detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches, **det_kw)
     else:
@@ -607,6 +644,12 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         GaussianDensityDetector.fit_rows((n_img - int(np.ceil(0.3 * n_img))) * (int(normality.shape[0]) // max(1, n_img)), split=False)
     elif scorer == 'gde':
         GaussianDensityDetector.fit_rows(int(normality.shape[0]))      # on every rank, before anybody waits for a broadcast
+    elif scorer == 'padim':
+        # on every rank, before anybody waits for a broadcast: the images the 70/30 split keeps, and the channel count
+        PositionGaussianDetector.fit_images(len(train_files))
+        if detector.channels > int(normality.shape[1]):
+            raise ValueError(f"channels must be a multiple of 32 in 32..{int(normality.shape[1])} (the rows' width), got "
+                             f"{detector.channels}")
     fit_kw = {} if groups is None else {"groups": groups}      # (the default bank: the reference's fit call, unchanged)
     if world > 1:
         # one bank for everybody: rank 0 draws the 70/30 split and fits, the others receive (bank, threshold) -- (state, threshold)
@@ -614,12 +657,15 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         if rank == 0:
             detector.fit(normality, **fit_kw)
             _print_coreset(detector)
-            payload = (detector.state() if scorer == 'gde' else detector.bank.cpu(), detector.threshold)
+            payload = (detector.state() if scorer in ('gde', 'padim') else detector.bank.cpu(), detector.threshold)
         state = broadcast_bank(payload if rank == 0 else None)
         if rank != 0:
             if scorer == 'gde':
                 detector = GaussianDensityDetector.from_state(state[0], patch_level=detector.patch_level, batch=detector.batch,
                                                               num_patches=detector.dim ** 2 if detector.dim else None)
+                detector.threshold = state[1]
+            elif scorer == 'padim':
+                detector = PositionGaussianDetector.from_state(state[0], batch=detector.batch, num_patches=detector.num_patches)
                 detector.threshold = state[1]
             else:
                 detector.bank, detector.threshold = AnomalyDetector._dev(state[0]), state[1]
@@ -694,25 +740,28 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
-          localization: str = 'patches'):
+          localization: str = 'patches', detector_options: dict = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours` and `localization` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization` and `detector_options` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns."""
     _check_detector(detector)
     _check_bank(bank)
     _check_coreset(coreset, detector)
     _check_image_scores(image_scores, neighbours, patch_localization, detector)
     _check_localization(localization, patch_localization)
+    _check_padim(detector, patch_localization, localization, bank, detector_options)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}
     score_kw = {} if image_scores is None else {"image_scores": image_scores, "neighbours": neighbours}
     if localization != 'patches':
         score_kw["localization"] = localization
+    if detector_options is not None:
+        score_kw["detector_options"] = detector_options
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'

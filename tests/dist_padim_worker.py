@@ -1,0 +1,57 @@
+"""Worker of tests/test_hip_padim.py::test_padim_two_ranks_equal_one_rank: one of two ranks that share the box's single GPU (gloo),
+each running tools.inference(detector='padim', localization='dense', bank='train') on the same tree and checkpoint, the datamodule
+pinned to the files' own 96 x 96 as in the test.  Rank 0 fits the per-position Gaussians and broadcasts (state, threshold); every
+rank returns the full maps.  Launched by `python -m torch.distributed.run`; prints `RESULT {...json...}` on rank 0 and saves rank 0's
+maps, image scores, embeddings and threshold for the one-rank comparison."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "self-supervised-anomaly-detection_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+SIZE = 96
+
+
+def main():
+    tmp, root, ck, channels = sys.argv[1], sys.argv[2], sys.argv[3], int(sys.argv[4])
+    os.environ.setdefault("SSAD_ALLOW_RANDOM_BACKBONE", "1")
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo")
+    from self_supervised import tools, datasets
+    datasets._DataModule.num_workers = 0
+    plain = datasets.MVTecDatamodule
+    tools.MVTecDatamodule = lambda r, **kw: plain(r, imsize=(SIZE, SIZE), **kw)
+    seen = {}
+    broadcast = tools.broadcast_bank
+
+    def spy(payload):                       # (state, threshold) as every rank holds it after the broadcast
+        got = broadcast(payload)
+        seen["threshold"] = float(got[1])
+        return got
+    tools.broadcast_bank = spy
+    np.random.seed(3)
+    out = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, detector='padim',
+                          localization='dense', bank='train', image_scores='max', detector_options={"channels": channels})
+    maps = out.anomaly_maps.contiguous()
+    mine = torch.cat([maps.reshape(-1), out.image_scores.reshape(-1).float(), torch.tensor([seen["threshold"]])]).contiguous()
+    parts = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, mine)
+    res = {"equal_across_ranks": all(torch.equal(parts[0], p) for p in parts), "shape": list(maps.shape),
+           "world": dist.get_world_size()}
+    if dist.get_rank() == 0:
+        torch.save({"maps": maps, "image_scores": out.image_scores, "embeddings": out.embedding_vectors,
+                    "threshold": seen["threshold"]}, os.path.join(tmp, "padim_rank0.pt"))
+        print("RESULT " + json.dumps(res), flush=True)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
