@@ -519,6 +519,35 @@ int ssad_rows_smallest_index(const float* m, int64_t Q, int R, int b, int cosine
 int ssad_rows_argmax(const float* s, int64_t Q, int P, float* val, int64_t* flat, void* stream);
 int ssad_knn_reweight(const float* xs, const float* bank_normalized, const int* mstar, const int* nbr, const float* smax, float* out,
                       int64_t Q, int D, int R, int bp, void* stream);
+/* The Euclidean metric of the kNN detector (csrc/knn_l2.hip; PatchCore's and SPADE's metric -- the reference has the cosine distance
+ * only).  d(q, b) = sqrt(max(|q|^2 + |b|^2 - 2 <q, b>, 0)) on the raw rows, formed in fp32: <q, b> by the MFMA chain of the cosine
+ * kernels (same tile, same K order) on unnormalised operands, the squared norms in the one summation order of ssad_row_sqnorms
+ * (the query norms are taken inside the kernels in that order), d2 = fmaxf((qn + bn) - 2 dot, 0).  Selection runs on d2; sqrtf is
+ * applied to the k winners only, so exact and near duplicates give finite distances >= 0.
+ * ssad_row_sqnorms: out[n] = sum_j x[n][j]^2, one wave per row in one fixed order that does not depend on N or on where the row
+ *   stands: equal rows give equal bits.  No atomics.
+ * ssad_l2_knn_fused / _split / _index / _index_split: the four cosine entry points above with that distance -- out[n] = the mean of
+ *   the k (1..3) smallest d, added smallest first; dist [N][k] / idx [N][k] = the k smallest (d2, bank row) pairs, lexicographic
+ *   (equal d2 to the smaller row), dist = sqrtf(d2).  bank [R][D] not normalised, bank_sq [R] = ssad_row_sqnorms(bank).  part as in
+ *   the cosine forms ([S][N][3] floats / 64-bit keys).  out, dist and idx are the same bits for every S and on every call, and the k
+ *   distances of the index form average to out's bits.  D % 32 == 0, D <= 65536, k <= R, 1 <= S <= 65535.
+ * ssad_l2_from_dots: out[q][r] = max(qsq[q] + bsq[r] - 2 sim[q][r], 0), SQUARED distances from dot products sim [Q][R] (the
+ *   expression above; feeds ssad_rows_smallest_index with cosine = 0).  out may be sim.  Q <= 65535.
+ * ssad_knn_reweight_l2: ssad_knn_reweight for this metric: d(x, r) = sqrt(sum_j (x[j] - bank[r][j])^2) by direct differences, the
+ *   weight in the shifted form 1 - exp(d(x_q, mstar[q]) - dmax) / sum_{j < bp} exp(d(x_q, nbr[q][j]) - dmax), dmax the largest of the
+ *   bp neighbour distances (Euclidean distances are not bounded by 2; expf overflows above 88).  A row outside 0 .. R - 1 counts as
+ *   distance 0.  1 <= bp <= 32. */
+int ssad_row_sqnorms(const float* x, float* out, int64_t N, int D, void* stream);
+int ssad_l2_knn_fused(const float* x, const float* bank, const float* bank_sq, float* out, int64_t N, int D, int R, int k, void* stream);
+int ssad_l2_knn_split(const float* x, const float* bank, const float* bank_sq, float* part, float* out, int64_t N, int D, int R, int k,
+                      int S, void* stream);
+int ssad_l2_knn_index(const float* x, const float* bank, const float* bank_sq, float* dist, int* idx, int64_t N, int D, int R, int k,
+                      void* stream);
+int ssad_l2_knn_index_split(const float* x, const float* bank, const float* bank_sq, void* part, float* dist, int* idx, int64_t N, int D,
+                            int R, int k, int S, void* stream);
+int ssad_l2_from_dots(const float* sim, const float* qsq, const float* bsq, float* out, int64_t Q, int R, void* stream);
+int ssad_knn_reweight_l2(const float* xs, const float* bank, const int* mstar, const int* nbr, const float* smax, float* out, int64_t Q,
+                         int D, int R, int bp, void* stream);
 /* Locally aware patch features from two stage maps of one trunk pass (csrc/patch_features.hip).  Replaces nothing in the reference,
  * which scores 841 windows per image (models.py:211-219); this is the feature construction of PatchCore (Roth et al., CVPR 2022,
  * section 3.1) as anomalib implements it: AvgPool2d(3, 1, 1) of every stage map, F.interpolate(mode='bilinear', align_corners=False)

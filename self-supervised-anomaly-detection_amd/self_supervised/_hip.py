@@ -52,6 +52,13 @@ SIGNATURES = {
     "ssad_rows_smallest_index": [_c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_rows_argmax": [_c_fp, _c_l, _c_i, _c_fp, _c_fp, _c_fp],
     "ssad_knn_reweight": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_row_sqnorms": [_c_fp, _c_fp, _c_l, _c_i, _c_fp],
+    "ssad_l2_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_from_dots": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_fp],
+    "ssad_knn_reweight_l2": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     "ssad_local_patch_features": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_coreset_greedy": [_c_fp, _c_l, _c_i, _c_i, _c_l, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_gaussian_fit_stats": [_c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp],

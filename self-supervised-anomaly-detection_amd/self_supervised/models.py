@@ -465,8 +465,19 @@ def coreset_size(coreset, r):
     return int(np.ceil(float(coreset) * int(r)))
 
 
+METRICS = ('cosine', 'euclidean')
+
+
+def check_metric(metric):
+    """ValueError unless `metric` is 'cosine' (the reference's distance) or 'euclidean' (PatchCore's and SPADE's)."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+    return metric
+
+
 def coreset_select(bank_n, m, coreset_dim=128):
-    """Greedy k-center coreset of the L2-normalised bank rows bank_n [R][D] (PatchCore): the selection runs on bank_n Omega
+    """Greedy k-center coreset of the bank rows bank_n [R][D] as the detector keeps them (L2-normalised with metric='cosine', raw
+    with 'euclidean'; PatchCore): the selection runs on bank_n Omega
     (coreset_projection(D, coreset_dim), one MFMA GEMM) or, with coreset_dim None, on bank_n itself, starting from row 0.
     Returns (sel int64 [m'] in selection order, rad float32 [m']) on the bank's device (ops.coreset_greedy)."""
     if coreset_dim is None:
@@ -486,15 +497,21 @@ class AnomalyDetector:
     `coreset` (opt-in; the reference keeps every row): None = the exact bank; a fraction f in (0, 1] or an int m >= 1 = ``fit`` keeps
     m = ceil(f R) (or m) of the R bank rows left after the split, chosen by a greedy k-center selection (coreset_select) on the
     normalised rows projected to `coreset_dim` dimensions (None: unprojected).  The bank is then those full-dimension normalised rows
-    in selection order, and the threshold is scored against it.  m >= R launches nothing: the exact bank."""
+    in selection order, and the threshold is scored against it.  m >= R launches nothing: the exact bank.
+
+    `metric` (opt-in): 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's: the bank keeps the raw rows plus
+    their squared norms `bank_sq`, every distance is sqrt(max(|x|^2 + |b|^2 - 2 <x, b>, 0)) (csrc/knn_l2.hip), the coreset is
+    selected on the raw rows, and the embedding width must be a multiple of 32 (ValueError otherwise: there is no unfused form)."""
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
-                 coreset_dim: int = 128) -> None:
+                 coreset_dim: int = 128, metric: str = 'cosine') -> None:
         self.patch_level = patch_level
         self.batch = batch
         self.dim = int(np.sqrt(num_patches)) if num_patches else None
         self.k = 3
         self.bank = None
+        self.bank_sq = None             # metric='euclidean': squared norms of the bank rows (ops.row_sqnorms)
+        self.metric = check_metric(metric)
         self.threshold = None
         self.coreset = check_coreset(coreset, coreset_dim)
         self.coreset_dim = coreset_dim
@@ -527,15 +544,40 @@ class AnomalyDetector:
             if m < r:
                 sel, rad = coreset_select(self.bank, m, self.coreset_dim)
                 self.bank = self.bank.index_select(0, sel).contiguous()
+                if self.bank_sq is not None:
+                    self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
                 self.coreset_rows = (sel, rad)
             self.coreset_counts = (int(self.bank.shape[0]), r)
         scores = self._scores(self._dev(val))
         self.threshold = torch.max(scores).item()
 
+    def _check_width(self, what, d):
+        if d % 32:
+            raise ValueError(f"{what}: metric='euclidean' needs an embedding width that is a multiple of 32, got {d}")
+
     def fit_bank(self, bank: Tensor) -> None:
+        if self.metric == 'euclidean':
+            self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
+            self.bank = self._dev(bank)
+            self.bank_sq = ops.row_sqnorms(self.bank)
+            return
         self.bank = ops.l2_normalize_rows(self._dev(bank))
 
+    def state(self):
+        """What another rank needs to score like this detector (tools.inference under torch.distributed): the metric and the bank
+        rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel."""
+        return {"metric": self.metric, "bank": self.bank.cpu()}
+
+    def load_state(self, state) -> None:
+        if state["metric"] != self.metric:
+            raise ValueError(f"load_state: the bank was fitted with metric={state['metric']!r}, this detector has {self.metric!r}")
+        self.bank = self._dev(state["bank"])
+        self.bank_sq = ops.row_sqnorms(self.bank) if self.metric == 'euclidean' else None
+
     def _scores(self, x):
+        if self.metric == 'euclidean':
+            self._check_width("predict", x.shape[1])
+            return ops.l2_knn_fused(x, self.bank, self.bank_sq, self.k)
         if x.shape[1] % 32 == 0 and 1 <= self.k <= 3:
             # normalise + similarity GEMM + k smallest distances in one kernel: no N x bank matrix in HBM (csrc/knn.hip)
             return ops.cosine_knn_fused(x, self.bank, self.k)
@@ -555,18 +597,21 @@ class AnomalyDetector:
 
     def kneighbors(self, x: Tensor, k: int = None):
         """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
-        idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by cosine distance, nearest first, equal
+        idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by the detector's metric, nearest first, equal
         distances to the smaller row.  idx indexes self.bank (after the split and the coreset).  Works at both levels."""
         if self.bank is None:
             raise ValueError("kneighbors: the detector has no bank (fit or fit_bank first)")
         x = self._dev(x)
         if x.shape[1] % 32:
             raise ValueError(f"kneighbors: the index kernel needs an embedding width that is a multiple of 32, got {x.shape[1]}")
-        dist, idx = ops.cosine_knn_index(x, self.bank, self.k if k is None else k)
+        if self.metric == 'euclidean':
+            dist, idx = ops.l2_knn_index(x, self.bank, self.bank_sq, self.k if k is None else k)
+        else:
+            dist, idx = ops.cosine_knn_index(x, self.bank, self.k if k is None else k)
         return dist, idx.long()
 
     def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = 9, scores: Tensor = None) -> Tensor:
-        """One score per image from the patch scores (patch level only; PatchCore eq. 6-7 with the cosine distance).  x [batch * P][D]
+        """One score per image from the patch scores (patch level only; PatchCore eq. 6-7 with the detector's metric).  x [batch * P][D]
         patch embeddings, image after image.  s_p = the patch scores predict returns (`scores`: that map, when the caller has it
         already); p* = argmax_p s_p, the smallest p on ties.
         'max': s_{p*}.  'reweighted': w s_{p*}, w = 1 - exp(d(x_{p*}, m*)) / sum_{r in N} exp(d(x_{p*}, r)) with m* the nearest
@@ -585,6 +630,13 @@ class AnomalyDetector:
         if mode == 'max':
             return smax
         xs = x.index_select(0, flat)                                     # x_{p*} of every image
+        if self.metric == 'euclidean':
+            _, mstar = ops.l2_knn_index(xs, self.bank, self.bank_sq, 1)
+            rows = mstar.reshape(-1).long()
+            dots = ops.linear_fwd(self.bank.index_select(0, rows), self.bank)                    # <B_{m*}, B_r>
+            d2 = ops.l2_from_dots(dots, self.bank_sq.index_select(0, rows), self.bank_sq)
+            _, nbr = ops.rows_smallest_index(d2, neighbours, cosine=False)
+            return ops.knn_reweight_l2(xs, self.bank, mstar, nbr, smax)
         _, mstar = ops.cosine_knn_index(xs, self.bank, 1)                # m*: an index pass over one row per image
         centre = self.bank.index_select(0, mstar.reshape(-1).long())     # B_{m*}
         sim = ops.linear_fwd(centre, self.bank)                          # [batch][R] similarities of B_{m*} to the bank

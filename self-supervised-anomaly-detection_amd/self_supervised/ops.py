@@ -827,6 +827,102 @@ def knn_reweight(xs, bank_n, mstar, nbr, smax):
     return out
 
 
+def row_sqnorms(x):
+    """x [N][D] -> [N] fp32 sum of squares of every row (csrc/knn_l2.hip ssad_row_sqnorms): one fixed summation order, equal rows give
+    equal bits wherever they stand."""
+    n, d = x.shape
+    out = _new((n,), x)
+    _run("row_sqnorms", 2.0 * n * d, 4.0 * (x.numel() + n),
+         lambda: _hip.lib().ssad_row_sqnorms(_hip.ptr(x), _hip.ptr(out), n, d, _hip.stream()))
+    return out
+
+
+def _check_l2_width(name, d):
+    if d % 32 or d > 65536:
+        raise ValueError(f"{name}: the Euclidean kernels need a width that is a multiple of 32 (at most 65536), got {d}")
+
+
+def l2_knn_fused(x, bank, bank_sq, k=3, splits=None):
+    """x [N][D], bank [R][D] (neither normalised), bank_sq = row_sqnorms(bank) -> [N] mean of the k smallest Euclidean distances
+    sqrt(max(|x|^2 + |b|^2 - 2 <x, b>, 0)) (csrc/knn_l2.hip ssad_l2_knn_fused / _split).  `splits`: None = the knn_splits rule; S >= 1 =
+    that many bank splits (1: one launch); the same bits for every S."""
+    n, d = x.shape
+    r = bank.shape[0]
+    k = int(k)
+    _check_l2_width("l2_knn_fused", d)
+    if not 1 <= k <= 3 or r < k:
+        raise ValueError(f"l2_knn_fused: k must be 1, 2 or 3 and at most the {r} bank rows, got {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"l2_knn_fused: splits must be >= 1, got {s}")
+    out = _new((n,), x)
+    if s == 1:
+        _run("l2_knn_fused", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n),
+             lambda: _hip.lib().ssad_l2_knn_fused(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(out), n, d, r, k,
+                                                  _hip.stream()))
+        return out
+    part = _new((s, n, 3), x)
+    _run("l2_knn_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n + 6 * part.numel()),
+         lambda: _hip.lib().ssad_l2_knn_split(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part), _hip.ptr(out), n, d, r, k,
+                                              s, _hip.stream()))
+    return out
+
+
+def l2_knn_index(x, bank, bank_sq, k=3, splits=None):
+    """kneighbors of the Euclidean bank: (dist [N][k] float32, idx [N][k] int32), the k (1..3) smallest (squared distance, bank row)
+    pairs of every query, ascending, equal ones to the smaller row; dist holds the roots -- the bits l2_knn_fused averages
+    (csrc/knn_l2.hip ssad_l2_knn_index / _split).  `splits` as in l2_knn_fused."""
+    n, d = x.shape
+    r = bank.shape[0]
+    k = int(k)
+    _check_l2_width("l2_knn_index", d)
+    if not 1 <= k <= 3:
+        raise ValueError(f"l2_knn_index: k must be 1, 2 or 3, got {k}")
+    if r < k:
+        raise ValueError(f"l2_knn_index: the bank has {r} rows, fewer than k = {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"l2_knn_index: splits must be >= 1, got {s}")
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    i32 = torch.int32
+    if s == 1:
+        _run("l2_knn_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + 2 * n * k),
+             lambda: _hip.lib().ssad_l2_knn_index(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(dist), _hip.ptr(idx, dtype=i32),
+                                                  n, d, r, k, _hip.stream()))
+        return dist, idx
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64)       # (squared-distance bits << 32 | row) keys
+    _run("l2_knn_index_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + 2 * n * k) + 16.0 * part.numel(),
+         lambda: _hip.lib().ssad_l2_knn_index_split(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part, dtype=torch.int64),
+                                                    _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d, r, k, s, _hip.stream()))
+    return dist, idx
+
+
+def l2_from_dots(sim, qsq, bsq):
+    """sim [Q][R] dot products, qsq [Q], bsq [R] squared norms -> [Q][R] SQUARED Euclidean distances max(qsq + bsq - 2 sim, 0)
+    (csrc/knn_l2.hip ssad_l2_from_dots; the kNN kernels' expression)."""
+    q, r = sim.shape
+    out = _new((q, r), sim)
+    _run("l2_from_dots", 3.0 * q * r, 8.0 * q * r,
+         lambda: _hip.lib().ssad_l2_from_dots(_hip.ptr(sim), _hip.ptr(qsq), _hip.ptr(bsq), _hip.ptr(out), q, r, _hip.stream()))
+    return out
+
+
+def knn_reweight_l2(xs, bank, mstar, nbr, smax):
+    """PatchCore's image-score weight on Euclidean distances (csrc/knn_l2.hip ssad_knn_reweight_l2): xs [Q][D], bank [R][D] (neither
+    normalised), mstar [Q] / [Q][1] int32 nearest bank rows, nbr [Q][b'] int32 neighbourhood rows, smax [Q] -> [Q]:
+    (1 - exp(d(x, mstar) - dmax) / sum_j exp(d(x, nbr_j) - dmax)) smax, dmax = max_j d(x, nbr_j)."""
+    q, d = xs.shape
+    r = bank.shape[0]
+    bp = nbr.shape[1]
+    out = _new((q,), xs)
+    i32 = torch.int32
+    _run("knn_reweight_l2", 3.0 * q * d * (bp + 1), 4.0 * q * d * (bp + 2),
+         lambda: _hip.lib().ssad_knn_reweight_l2(_hip.ptr(xs), _hip.ptr(bank), _hip.ptr(mstar, dtype=i32), _hip.ptr(nbr, dtype=i32),
+                                                 _hip.ptr(smax), _hip.ptr(out), q, d, r, bp, _hip.stream()))
+    return out
+
+
 def bilinear_taps(nf, nc):
     """The sample positions csrc/patch_features.hip uses to resample nc positions to nf (F.interpolate's align_corners=False rule in
     integer arithmetic): per destination index i, num = max((2 i + 1) nc - nf, 0), a = num // (2 nf), b = min(a + 1, nc - 1) and the

@@ -18,7 +18,7 @@ from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
 from .models import (AnomalyDetector, GaussianDensityDetector, PeraNet, PositionGaussianDetector, check_coreset,
-                     check_image_scores)
+                     check_image_scores, check_metric)
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -385,6 +385,15 @@ def _check_coreset(coreset, detector):
     return check_coreset(coreset)
 
 
+def _check_metric(metric, detector):
+    """The metric option of the kNN detector (models.check_metric): 'euclidean' is PatchCore's distance between raw rows; the
+    Gaussian detectors have a metric of their own (Mahalanobis)."""
+    check_metric(metric)
+    if metric != 'cosine' and detector != 'knn':
+        raise ValueError(f"metric={metric!r} applies to detector='knn' only: detector={detector!r} scores by its Mahalanobis distance")
+    return metric
+
+
 def _check_image_scores(image_scores, neighbours, patch_localization, detector):
     """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
     scores and their nearest bank rows, which the image level and the Gaussian do not have."""
@@ -473,7 +482,7 @@ def _train_bank_rows(per_image, n_total, device):
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
               coreset=None, image_scores: str = None, neighbours: int = 9,
-              localization: str = 'patches', detector_options: dict = None) -> ModelOutputsContainer:
+              localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine') -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -492,8 +501,11 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     detector='padim' = one Gaussian per map position (PositionGaussianDetector: PaDiM; the Mahalanobis distance to the position's
     Gaussian over `channels` randomly chosen columns); needs patch_localization=True, localization='dense' and bank='train'; takes
     image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed'} of that detector
-    ('padim' only)."""
+    ('padim' only).
+    `metric`: 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's Euclidean distance between the raw rows
+    (AnomalyDetector(metric='euclidean'): search, coreset selection and image scores all in that metric); 'knn' only."""
     scorer = _check_detector(detector)
+    _check_metric(metric, scorer)
     _check_localization(localization, patch_localization)
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, scorer)
@@ -587,6 +599,8 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     groups = None
     kind = {'gde': GaussianDensityDetector, 'padim': PositionGaussianDetector}.get(scorer, AnomalyDetector)
     det_kw = dict(padim_kw) if scorer == 'padim' else ({} if coreset is None else {"coreset": coreset})
+    if metric != 'cosine':
+        det_kw["metric"] = metric
     if patch_localization:
         detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches, **det_kw)
     else:
@@ -657,7 +671,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         if rank == 0:
             detector.fit(normality, **fit_kw)
             _print_coreset(detector)
-            payload = (detector.state() if scorer in ('gde', 'padim') else detector.bank.cpu(), detector.threshold)
+            payload = (detector.state(), detector.threshold)
         state = broadcast_bank(payload if rank == 0 else None)
         if rank != 0:
             if scorer == 'gde':
@@ -668,7 +682,8 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
                 detector = PositionGaussianDetector.from_state(state[0], batch=detector.batch, num_patches=detector.num_patches)
                 detector.threshold = state[1]
             else:
-                detector.bank, detector.threshold = AnomalyDetector._dev(state[0]), state[1]
+                detector.load_state(state[0])         # the bank carries its metric; bank_sq is recomputed here, the same bits
+                detector.threshold = state[1]
     else:
         detector.fit(normality, **fit_kw)
         _print_coreset(detector)
@@ -740,15 +755,16 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
-          localization: str = 'patches', detector_options: dict = None):
+          localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine'):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization` and `detector_options` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options` and `metric` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns."""
     _check_detector(detector)
+    _check_metric(metric, detector)
     _check_bank(bank)
     _check_coreset(coreset, detector)
     _check_image_scores(image_scores, neighbours, patch_localization, detector)
@@ -762,6 +778,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw["localization"] = localization
     if detector_options is not None:
         score_kw["detector_options"] = detector_options
+    if metric != 'cosine':
+        score_kw["metric"] = metric
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
