@@ -280,6 +280,23 @@ int ssad_conv3x3_c64_op(const float* in, const float* w_ohwi, float* out, const 
 int ssad_conv3x3_c64_eval(const float* in, const float* w_ohwi, float* out, const float* scale, const float* shift,
                           const float* residual, int relu, int64_t N, int H, int W, int in_hwnc, int out_hwnc, int res_hwnc,
                           void* stream);
+/* The launch geometry of the three 3 x 3 / stride 1 / pad 1 kernels -- the launchers take their values from the same functions.
+ * Host-only (no GPU needed); test aid (tests/test_conv3x3_table.py pins it), no reference counterpart.
+ *   SSAD_CONV3X3_C64  ssad_conv3x3_c64 / _op / _h / _eval (Cin = Cout = 64; one workgroup per 8 x 16 tile)
+ *   SSAD_CONV3X3_H    ssad_conv3x3_h
+ *   SSAD_CONV3X3_W    ssad_conv3x3_hw (is_float 0) / ssad_conv3x3_fw, _fw_eval (is_float 1), WITHOUT the minimum-work rule of
+ *                     ssad_conv3x3_hw_ok / _fw_ok (the entry points have none)
+ * out[0] instantiation: C64 816; H: bn * 10 + tw8 (bn = channels per workgroup, 64 / 128; tw8 = two 8-row strips of a map up to 8
+ *        wide per tile); W: wn * 10000 + tw8 * 1000 + twp * 100 + channels per input chunk (wn = 64-channel wave columns; tw8 = four
+ *        8 x 8 maps per tile; twp = two 16 x 16 maps per tile)
+ * out[1] ntiles   out[2] gx (workgroups per channel slab = rows of the statistics workspace)   out[3] gy (channel slabs)
+ * out[4] input chunks per tile   out[5] maps present in the last tile   out[6] most tiles one workgroup walks, ceil(ntiles / gx)
+ * out[7] maps per tile
+ * Returns non-zero (out untouched) for a path or a shape the entry point refuses. */
+#define SSAD_CONV3X3_C64 0
+#define SSAD_CONV3X3_H 1
+#define SSAD_CONV3X3_W 2
+int ssad_conv3x3_geometry(int path, int64_t N, int H, int W, int Cin, int Cout, int is_float, int64_t* out);
 /* Weight gradient of the 3x3 / stride 1 / pad 1 convolutions (Cin, Cout multiples of 64) as a halo-tile kernel: a workgroup
  * owns a 64 x 64 (co, ci) block for all nine taps and walks over pixel tiles (csrc/wgrad_halo.hip).  Same contract as
  * ssad_conv_wgrad: slab[splits][Cout][9 * Cin] with splits = ssad_wgrad3x3_halo_splits(...), then ssad_wgrad_reduce. */

@@ -61,6 +61,11 @@ int wgrad_halo16_tile(int Wo);
 int wgrad_g16_tile(int Wo, int stride);
 int stem_wgrad_kernel_id(int dz_half);
 
+// SSAD_CONV3X3_C64 / SSAD_CONV3X3_H of ssad_conv3x3_geometry (conv16w.hip), from the launchers' own geometry functions in
+// conv_c64.hip / conv16.hip; out[8] as documented in include/ssad.h
+int conv3x3_c64_geometry(int64_t N, int H, int W, int Cin, int Cout, int64_t* out);
+int conv3x3_h_geometry(int64_t N, int H, int W, int Cin, int Cout, int64_t* out);
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Storage type of an activation tensor: float, or _Float16 for the precision-16 step whose tensors live in HBM as halves (what

@@ -482,15 +482,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_h_kernel(Conv16Params p) {
 struct Geo {
     bool tw8;
     int tiles_y, tiles_x, bn, gx, gy;
+    int nchunks;              // input chunks (CK channels) per tile
+    int per, last;            // maps (8-row strips of a map up to 8 wide) per tile, and those present in the last tile
     int64_t ntiles;
 };
 
-static Geo geometry(int64_t N, int H, int W, int Cout) {
+// Cin only sets nchunks
+static Geo geometry(int64_t N, int H, int W, int Cout, int Cin = CK) {
     Geo g;
     g.tw8 = W <= 8;
     g.tiles_y = (H + 7) / 8;
     g.tiles_x = g.tw8 ? 1 : (W + 15) / 16;
+    g.per = g.tw8 ? 2 : 1;
     g.ntiles = g.tw8 ? (N * g.tiles_y + 1) / 2 : N * g.tiles_y * g.tiles_x;
+    g.last = g.tw8 ? (int)(N * g.tiles_y - 2 * (g.ntiles - 1)) : 1;
+    g.nchunks = Cin / CK;
     g.bn = Cout % 128 == 0 ? 128 : 64;
     g.gy = Cout / g.bn;
     // persistent workgroups: two per CU over all channel slabs
@@ -503,6 +509,16 @@ static Geo geometry(int64_t N, int H, int W, int Cout) {
 }
 
 }  // namespace
+
+// SSAD_CONV3X3_H of ssad_conv3x3_geometry (conv16w.hip): the values ssad_conv3x3_h launches with
+int conv3x3_h_geometry(int64_t N, int H, int W, int Cin, int Cout, int64_t* out) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || Cin > 1024 || N * (int64_t)H * W >= (int64_t)1 << 31)
+        return 1;
+    const Geo g = geometry(N, H, W, Cout, Cin);            // the call ssad_conv3x3_h makes
+    out[0] = g.bn * 10 + (g.tw8 ? 1 : 0); out[1] = g.ntiles; out[2] = g.gx; out[3] = g.gy; out[4] = g.nchunks; out[5] = g.last;
+    out[6] = (g.ntiles + g.gx - 1) / g.gx; out[7] = g.per;
+    return 0;
+}
 
 // 1 when ssad_conv3x3_h handles the layer (channel counts multiples of 64).
 extern "C" int ssad_conv3x3_h_ok(int Cin, int Cout) {
@@ -533,13 +549,13 @@ extern "C" int ssad_conv3x3_h(const void* in, const void* w_ohwi, void* out, con
     SSAD_CHECK_ARG(!stats_ws || (mean && invstd), "statistics need mean / invstd outputs");
     SSAD_CHECK_ARG(!emit || tr_mean, "emit without an input transform");
     SSAD_CHECK_ARG(N * (int64_t)H * W < (int64_t)1 << 31, "too many pixels for one launch");
-    const Geo g = geometry(N, H, W, Cout);
+    const Geo g = geometry(N, H, W, Cout, Cin);
     Conv16Params p;
     p.in = (const hf*)in; p.wt = (const hf*)w_ohwi; p.out = (hf*)out; p.residual = (const hf*)residual;
     p.tr_mean = tr_mean; p.tr_invstd = tr_invstd; p.tr_gamma = tr_gamma; p.tr_beta = tr_beta; p.emit = (hf*)emit;
     p.stats = stats_ws;
     p.N = (int)N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.tiles_y = g.tiles_y; p.tiles_x = g.tiles_x; p.nchunks = Cin / CK; p.ntiles = g.ntiles;
+    p.tiles_y = g.tiles_y; p.tiles_x = g.tiles_x; p.nchunks = g.nchunks; p.ntiles = g.ntiles;
     const dim3 grid((unsigned)g.gx, (unsigned)g.gy);
     hipStream_t st = (hipStream_t)stream;
     const int lds_bytes = ((g.tw8 ? 200 : 180) * LDP + 2 * g.bn * LDP) * 2 + (tr_mean ? 16 * Cin : 0);

@@ -28,6 +28,7 @@
 // Workgroups are persistent over tiles of ONE channel slab (blockIdx.y), so the BatchNorm statistics of the stored output stay in
 // registers (per tile in fp32, across tiles in double) and leave as one partial row per workgroup.
 #include "common.h"
+#include "ssad.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -772,10 +773,13 @@ __global__ __launch_bounds__(256) void pack_hw_kernel(const float* __restrict__ 
 struct GeoW {
     bool tw8, ck32, twp;
     int tiles_y, tiles_x, wn, gx, gy;
+    int ck, nchunks;          // input channels per chunk (128-byte rows; 64-byte rows for 16 x 32 tiles), chunks per tile
+    int per, last;            // maps per tile, maps present in the last tile
     int64_t ntiles;
 };
 
-static GeoW geometry_w(int64_t N, int H, int W, int Cout) {
+// esize: bytes per tensor element (2 halves, 4 floats).  Cin only sets nchunks (the dispatch rules do not need it).
+static GeoW geometry_w(int64_t N, int H, int W, int Cout, int Cin = 64, int esize = 2) {
     GeoW g;
     g.tw8 = H == 8 && W == 8;
     g.wn = Cout % 128 == 0 ? 2 : 1;
@@ -783,7 +787,11 @@ static GeoW geometry_w(int64_t N, int H, int W, int Cout) {
     g.twp = g.wn == 1 && H == 16 && W == 16;               // 16 x 16 maps of 64 channels: two maps per tile
     g.tiles_y = g.tw8 ? 1 : H / 16;
     g.tiles_x = g.tw8 ? 1 : W / (g.wn == 1 ? 32 : 16);
-    g.ntiles = g.tw8 ? (N + 3) / 4 : g.twp ? (N + 1) / 2 : N * g.tiles_y * g.tiles_x;
+    g.per = g.tw8 ? 4 : g.twp ? 2 : 1;
+    g.ntiles = g.per > 1 ? (N + g.per - 1) / g.per : N * g.tiles_y * g.tiles_x;
+    g.last = g.per > 1 ? (int)(N - (int64_t)g.per * (g.ntiles - 1)) : 1;
+    g.ck = (g.ck32 ? 64 : 128) / esize;
+    g.nchunks = Cin / g.ck;
     g.gy = Cout / (64 * g.wn);
     static const int slots = getenv("SSAD_CONV16W_WGS") ? atoi(getenv("SSAD_CONV16W_WGS")) : 256;      // one workgroup per CU
     int64_t gx = slots / g.gy;
@@ -796,6 +804,11 @@ static GeoW geometry_w(int64_t N, int H, int W, int Cout) {
 // bytes of the two halo stages (+ 16 KB: the largest transform table); CKB = bytes of a chunk row (128, or 64 for 16 x 32 tiles)
 static constexpr int lds_bytes_w(bool wn1, bool tw8, bool twp = false) {
     return 2 * (tw8 ? 400 : twp ? 648 : 18 * (wn1 ? 34 : 18)) * ((wn1 ? 64 : 128) + 16) + 16 * 1024;
+}
+
+// the maps conv_impl takes (it needs no minimum amount of work: that is shape_ok's, for the dispatch)
+static bool maps_ok(int H, int W, int Cout) {
+    return (H == 8 && W == 8 && Cout % 128 == 0) || (H == 16 && W == 16) || (H > 0 && W > 0 && H % 16 == 0 && W % (Cout % 128 == 0 ? 16 : 32) == 0);
 }
 
 static int shape_ok(int64_t N, int H, int W, int Cin, int Cout) {
@@ -835,10 +848,10 @@ static int conv_impl(const T* in, const T* w_packed, T* out, const T* residual, 
                      const float* tr_invstd, const float* tr_gamma, const float* tr_beta, T* emit, int64_t N, int H, int W, int Cin,
                      int Cout, double* stats_ws, float eps, float momentum, float* mean, float* invstd, float* running_mean,
                      float* running_var, void* stream, const float* shift = nullptr, int relu = 0, int out_hwnc = 0) {
-    constexpr int CKW = 128 / (int)sizeof(T), CKN = 64 / (int)sizeof(T);     // channels per chunk: 128-byte rows; 64-byte rows for 16 x 32 tiles
+    constexpr int CKW = 128 / (int)sizeof(T), CKN = 64 / (int)sizeof(T);     // the kernels' chunk widths (geometry_w: g.ck)
     SSAD_CHECK_ARG(in && w_packed && out && N > 0 && H > 0 && W > 0, "bad argument");
     SSAD_CHECK_ARG(Cin % 64 == 0 && Cout % 64 == 0 && Cin <= 1024, "channel counts must be multiples of 64 (Cin <= 1024)");
-    SSAD_CHECK_ARG((H == 8 && W == 8 && Cout % 128 == 0) || (H == 16 && W == 16) || (H % 16 == 0 && W % (Cout % 128 == 0 ? 16 : 32) == 0),
+    SSAD_CHECK_ARG(maps_ok(H, W, Cout),
                    "maps of 16 x 16 blocks (16 x 32 when Cout is not a multiple of 128, or 16 x 16 maps), or 8 x 8 maps with Cout a multiple of 128");
     SSAD_CHECK_ARG(!(shift || out_hwnc) || (std::is_same<T, float>::value && !stats_ws), "inference epilogue / position-major output: float, no statistics");
     SSAD_CHECK_ARG(!tr_mean || (tr_invstd && tr_gamma && tr_beta), "input transform needs mean, invstd, gamma, beta");
@@ -846,7 +859,8 @@ static int conv_impl(const T* in, const T* w_packed, T* out, const T* residual, 
     SSAD_CHECK_ARG(!emit || tr_mean, "emit without an input transform");
     SSAD_CHECK_ARG(!res_mask || residual, "a residual mask without a residual");
     SSAD_CHECK_ARG(N * (int64_t)H * W < (int64_t)1 << 31, "too many pixels for one launch");
-    const GeoW g = geometry_w(N, H, W, Cout);
+    const GeoW g = geometry_w(N, H, W, Cout, Cin, (int)sizeof(T));
+    SSAD_CHECK_ARG(g.ck == (g.ck32 ? CKN : CKW), "chunk width out of step with the kernel instantiations");
     HWParams<T> p;
     p.in = in; p.wp = w_packed; p.out = out; p.residual = residual; p.res_mask = res_mask;
     p.tr_mean = tr_mean; p.tr_invstd = tr_invstd; p.tr_gamma = tr_gamma; p.tr_beta = tr_beta; p.emit = emit;
@@ -858,7 +872,7 @@ static int conv_impl(const T* in, const T* w_packed, T* out, const T* residual, 
     p.trace = conv16w_trace_buf;
 #endif
     p.N = (int)N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.tiles_y = g.tiles_y; p.tiles_x = g.tiles_x; p.nchunks = Cin / (g.ck32 ? CKN : CKW); p.ntiles = g.ntiles;
+    p.tiles_y = g.tiles_y; p.tiles_x = g.tiles_x; p.nchunks = g.nchunks; p.ntiles = g.ntiles;
     const dim3 grid((unsigned)g.gx, (unsigned)g.gy);
     hipStream_t st = (hipStream_t)stream;
     static bool attr_set = false;
@@ -893,6 +907,23 @@ static int conv_impl(const T* in, const T* w_packed, T* out, const T* residual, 
 }
 
 }  // namespace
+
+// The launch geometry of the three 3 x 3 / stride 1 kernels, as their launchers compute it (geometry_w above, geometry() of conv16.hip,
+// the tile arithmetic of conv_c64.hip): see include/ssad.h.  Host only.
+extern "C" int ssad_conv3x3_geometry(int path, int64_t N, int H, int W, int Cin, int Cout, int is_float, int64_t* out) {
+    if (!out) return 1;
+    if (path == SSAD_CONV3X3_C64) return conv3x3_c64_geometry(N, H, W, Cin, Cout, out);
+    if (path == SSAD_CONV3X3_H) return conv3x3_h_geometry(N, H, W, Cin, Cout, out);
+    if (path != SSAD_CONV3X3_W) return 1;
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || Cin > 1024 || !maps_ok(H, W, Cout) ||
+        N * (int64_t)H * W >= (int64_t)1 << 31)
+        return 1;
+    const GeoW g = geometry_w(N, H, W, Cout, Cin, is_float ? 4 : 2);          // the call conv_impl makes
+    out[0] = g.wn * 10000 + (g.tw8 ? 1000 : 0) + (g.twp ? 100 : 0) + g.ck;
+    out[1] = g.ntiles; out[2] = g.gx; out[3] = g.gy; out[4] = g.nchunks; out[5] = g.last;
+    out[6] = (g.ntiles + g.gx - 1) / g.gx; out[7] = g.per;
+    return 0;
+}
 
 // 1 when ssad_conv3x3_hw takes the launch: channel counts multiples of 64, maps of 16 x 16 blocks (16 x 32 for 64 output channels; or
 // 8 x 8 maps), and enough (tile, channel slab) pairs to give every CU a workgroup (smaller launches stay on csrc/conv16.hip).

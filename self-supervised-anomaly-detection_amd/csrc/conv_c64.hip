@@ -423,10 +423,32 @@ static int c64_stagger(int64_t nwg) {
     return nwg >= 4 * 512 ? st : 0;
 }
 
+// tiles of a launch: one workgroup per 8 x 16 tile (what ssad_conv3x3_geometry reports is what the launchers below use)
+struct GeoC64 {
+    int tiles_y, tiles_x;
+    int64_t nwg;
+};
+static GeoC64 geometry_c64(int64_t N, int H, int W) {
+    GeoC64 g;
+    g.tiles_y = (H + TH - 1) / TH;
+    g.tiles_x = (W + TW - 1) / TW;
+    g.nwg = N * g.tiles_y * g.tiles_x;
+    return g;
+}
+
 }  // namespace
 
+// SSAD_CONV3X3_C64 of ssad_conv3x3_geometry (conv16w.hip)
+int conv3x3_c64_geometry(int64_t N, int H, int W, int Cin, int Cout, int64_t* out) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin != C || Cout != C) return 1;
+    const GeoC64 g = geometry_c64(N, H, W);
+    if (g.nwg >= (int64_t)2147483647) return 1;
+    out[0] = TH * 100 + TW; out[1] = g.nwg; out[2] = g.nwg; out[3] = 1; out[4] = 1; out[5] = 1; out[6] = 1; out[7] = 1;
+    return 0;
+}
+
 extern "C" int64_t ssad_conv3x3_c64_stats_rows(int64_t N, int H, int W) {
-    return N * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
+    return geometry_c64(N, H, W).nwg;
 }
 
 // out = conv3x3(pad 1, stride 1)(T(in)) (+ residual [* res_mask]), 64 -> 64 channels, NHWC fp32, OHWI weights.
@@ -454,8 +476,9 @@ static int conv3x3_c64_impl(const float* in, const float* w_ohwi, float* out, co
     p.stats = stats_ws;
     p.scale = p.shift = nullptr; p.relu = 0; p.in_ps = p.out_ps = p.res_ps = C; p.in_ss = p.out_ss = p.res_ss = (int64_t)H * W * C;
     p.N = (int)N; p.H = H; p.W = W;
-    p.tiles_y = (H + TH - 1) / TH; p.tiles_x = (W + TW - 1) / TW;
-    const int64_t nwg = N * p.tiles_y * p.tiles_x;
+    const GeoC64 g = geometry_c64(N, H, W);
+    p.tiles_y = g.tiles_y; p.tiles_x = g.tiles_x;
+    const int64_t nwg = g.nwg;
     SSAD_CHECK_ARG(nwg < (int64_t)2147483647, "too many tiles for one launch");
     p.stagger = c64_stagger(nwg);
     static const int lds_bytes = LDS_BYTES + (getenv("SSAD_C64_LDS_PAD") ? atoi(getenv("SSAD_C64_LDS_PAD")) : 0);   // residency experiments
@@ -518,8 +541,9 @@ extern "C" int ssad_conv3x3_c64_eval(const float* in, const float* w_ohwi, float
     p.out_ps = out_hwnc ? N * C : C; p.out_ss = out_hwnc ? C : (int64_t)H * W * C;
     p.res_ps = res_hwnc ? N * C : C; p.res_ss = res_hwnc ? C : (int64_t)H * W * C;
     p.N = (int)N; p.H = H; p.W = W;
-    p.tiles_y = (H + TH - 1) / TH; p.tiles_x = (W + TW - 1) / TW;
-    const int64_t nwg = N * p.tiles_y * p.tiles_x;
+    const GeoC64 g = geometry_c64(N, H, W);
+    p.tiles_y = g.tiles_y; p.tiles_x = g.tiles_x;
+    const int64_t nwg = g.nwg;
     SSAD_CHECK_ARG(nwg < (int64_t)2147483647, "too many tiles for one launch");
     p.stagger = c64_stagger(nwg);
     static bool attr_set = false;

@@ -561,6 +561,22 @@ def conv3x3_hw(x, w_packed, cout, residual=None, transform=None, emit=False, sta
     return res[0] if len(res) == 1 else tuple(res)
 
 
+# Launch geometry of the 3x3 / stride 1 kernels (ssad_conv3x3_geometry, include/ssad.h): what the launchers themselves compute
+CONV3X3_C64, CONV3X3_H, CONV3X3_W = 0, 1, 2
+CONV3X3_GEOMETRY_FIELDS = ("inst", "ntiles", "gx", "gy", "chunks", "last", "walk", "per")
+
+
+def conv3x3_geometry(path, n, h, w, cin, cout, f32=False):
+    """The launch of ssad_conv3x3_c64* (CONV3X3_C64), ssad_conv3x3_h (CONV3X3_H) or ssad_conv3x3_hw / _fw / _fw_eval (CONV3X3_W, f32 for
+    the float form) on n maps of h x w: a dict of the instantiation id, ntiles, gx, gy, input chunks per tile, maps present in the last
+    tile, the most tiles one workgroup walks and the maps per tile -- or None where the entry point refuses the shape.  No GPU needed."""
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    if _hip.lib().ssad_conv3x3_geometry(int(path), n, h, w, cin, cout, int(bool(f32)), out):
+        return None
+    return dict(zip(CONV3X3_GEOMETRY_FIELDS, (int(v) for v in out)))
+
+
 def conv3x3_fw_eval_ok(n, h, w, cin, cout):
     return bool(_hip.lib().ssad_conv3x3_fw_eval_ok(n, h, w, cin, cout))
 
