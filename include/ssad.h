@@ -614,6 +614,23 @@ int ssad_position_gaussian_fit_stats(const float* x, const int* sel, int n_img, 
                                      void* stream);
 int ssad_position_mahalanobis(const float* x, const int* sel, const float* mu_hi, const float* mu_lo, const float* w, float* out,
                               int n_img, int64_t P, int D, int d, void* stream);
+/* The step between the two above, on the device (csrc/padim.hip): per position p, all in fp64,
+ *   Sigma = scatter[p] / (n - 1) + eps I,  C = the lower Cholesky factor of Sigma,  W = C^-1 (lower triangular).
+ * mean [P][d] and scatter [P][d][d] are what ssad_position_gaussian_fit_stats wrote.  Only the lower triangle of scatter (diagonal
+ * included) is read; scatter is the WORKSPACE and is overwritten, Sigma -> C -> W in place in that triangle (LAPACK's potrf +
+ * trtri), the upper triangle is neither read nor written.
+ * Out: w [P][d][d] fp32 = W rounded once, exact +0.0f above the diagonal; mu_hi = fp32(mean), mu_lo = fp32(mean - mu_hi) (the float
+ * pair ssad_position_mahalanobis takes); c_out / w64_out [P][d][d] fp64 (either may be NULL) = C / W before the rounding, zeros above
+ * the diagonal; info [P] = 0, or 1 + the column of the first pivot that is not finite and positive (LAPACK's info).  A position with
+ * info != 0 has w (and c_out, w64_out) filled with NaN and its mu written; the other positions are not affected.  A bad pivot is a
+ * status: the kernel neither loops nor traps on it.
+ * Arithmetic: fp64 FMA only, nothing in fp32 before the final rounding.  Every element is (a - sum_k l_k b_k) / pivot as one fma
+ * chain with k ascending and a true division; one workgroup owns one matrix, no atomics and no sum split across workgroups: the same
+ * bits on every call, and position p of a P-position launch equals the same matrix launched as P = 1.
+ * d % 32 == 0, 32 <= d <= 512; 1 <= P < 2^31; n >= 2; eps > 0; no pointer NULL but c_out / w64_out; anything else returns the
+ * argument error without a launch. */
+int ssad_position_gaussian_factor(const double* mean, double* scatter, int64_t P, int d, int64_t n, double eps, float* mu_hi,
+                                  float* mu_lo, float* w, double* c_out, double* w64_out, int* info, void* stream);
 /* HOST function (no GPU work): per-channel integer sums of the window [top, top + h) x [left, left + w) of the NEAREST affine
  * transform of an H x W x 3 uint8 image (fix: the six 16.16 coefficients of ssad_aug_params.aff_fix; NULL: the image itself),
  * zero outside the image.  The sampler's colour-similarity test (datasets.py:300-312) needs this mean between two random

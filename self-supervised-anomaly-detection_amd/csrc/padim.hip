@@ -3,9 +3,10 @@
 // has its own Gaussian over the n_img fit images and the Mahalanobis distance to it is the pixel score.  The reference repository has
 // no such scorer: the yardstick is numpy.cov + scipy's mahalanobis in float64 (tests/padim_ref.py).
 //
-// Two entry points, the batched forms of gde.hip's:
+// Three entry points, the first and the last the batched forms of gde.hip's:
 //  * ssad_position_gaussian_fit_stats: per position the mean and the centred scatter matrix of the selected columns in fp64; the
-//    regulariser, the P Cholesky factors and their triangular inverses are a one-off on the host (self_supervised/density.py);
+//    regulariser, the P Cholesky factors and their triangular inverses are a one-off on the host (self_supervised/density.py), or
+//  * ssad_position_gaussian_factor (factor='device'): the same step in fp64 on the device, in place in the scatter buffer;
 //  * ssad_position_mahalanobis: out[n P + p] = ||W_p (x_sel - mu_p)||_2 in ONE kernel on the fp32 matrix cores --
 //    mahalanobis_fused_kernel's tile (gde.hip) with a workgroup that owns one position and 128 images: W and the mean are that
 //    position's, the query rows are gathered through `sel` at a stride of P D floats between images.
@@ -244,6 +245,197 @@ bool padim_shape_ok(int n_img, int64_t P, int D, int d) {
     return n_img >= 1 && P >= 1 && D > 0 && D % 4 == 0 && d % 32 == 0 && d >= 32 && d <= D;
 }
 
+// ================================================ covariance factor (fp64) ================================================
+// Per position: Sigma = scatter / (n - 1) + eps I -> C = chol(Sigma) -> W = C^-1, in place in the lower triangle of the scatter
+// buffer (the upper triangle is neither read nor written).  One workgroup of d threads owns one matrix and thread i owns ROW i for
+// the whole kernel: what a thread reads from global memory is its own row, written by itself, except the 32 x 32 blocks staged
+// through LDS.  Both phases walk 32-column blocks; the O(d^3) part of each is one routine, rank32: a row's 32 accumulators take
+// 32 columns of that row times a 32 x 32 block that every thread reads from LDS at the same address (a broadcast).
+//  * Cholesky, left-looking: block column J starts from Sigma (formed here, where each element of the lower triangle is read
+//    exactly once), takes the block columns K < J (rank32 with L[J][K] staged), the 32 x 32 diagonal block is factored in LDS, the
+//    rows below solve against it.
+//  * Inverse, by forward substitution down block column J = 0, 1, ..: W[K][J] = C[K][K]^-1 (delta_KJ I - sum_{J <= K' < K} C[K][K']
+//    W[K'][J]).  Block column J of W replaces block column J of C, which the later columns no longer need; the sums are carried in
+//    the rows' accumulators (rank32 with W[K][J] staged), the 32 x 32 solve has one thread per column.
+// Every element is (a - sum_k l_k b_k) / pivot as ONE fma chain with k ascending and a true division: Higham's Lemma 8.4, hence
+// the componentwise bounds of his Theorems 10.3 (Cholesky) and 8.5 (substitution) with their textbook constants.  No atomics, no
+// split of a sum: the same bits on every call and for every P.
+constexpr int FB = 32, FLD = 34, FDG = 33, FACTOR_MAX_D = 512;
+
+struct FactorParams {
+    const double* mean;   // [P][d]
+    double* a;            // [P][d][d] scatter in, workspace
+    float* mu_hi;         // [P][d]
+    float* mu_lo;         // [P][d]
+    float* w;             // [P][d][d]
+    double* c_out;        // [P][d][d] or null
+    double* w64_out;      // [P][d][d] or null
+    int* info;            // [P]
+    int d;
+    double nm1, eps;
+};
+
+// acc[c] -= sum_k l[k] B[c][k], k ascending
+__device__ __forceinline__ void rank32(double (&acc)[FB], const double (&l)[FB], const double (*B)[FLD]) {
+#pragma unroll
+    for (int k = 0; k < FB; k += 2)
+#pragma unroll
+        for (int c = 0; c < FB; ++c) {
+            const double2 b = *(const double2*)&B[c][k];
+            acc[c] = fma(-l[k], b.x, acc[c]);
+            acc[c] = fma(-l[k + 1], b.y, acc[c]);
+        }
+}
+
+__global__ __launch_bounds__(FACTOR_MAX_D) void position_factor_kernel(FactorParams q) {
+    __shared__ __attribute__((aligned(16))) double B[FB][FLD];     // the staged block, B[c][k]
+    __shared__ double Dg[FB][FDG];                                  // a diagonal block
+    __shared__ double Sb[FB][FDG];                                  // right-hand sides of the 32 x 32 solve
+    __shared__ int fail;
+    const int d = q.d, nb = d / FB, i = threadIdx.x, nt = blockDim.x;      // nt == d
+    const int ib = i / FB, r = i % FB;
+    const int64_t p = blockIdx.x, dd = (int64_t)d * d;
+    double* A = q.a + p * dd;
+    double* row = A + (int64_t)i * d;
+    {
+        const double m = q.mean[p * d + i];
+        const float hi = (float)m;
+        q.mu_hi[p * d + i] = hi;
+        q.mu_lo[p * d + i] = (float)(m - (double)hi);
+    }
+    if (i == 0) fail = 0;
+    __syncthreads();
+    double acc[FB], l[FB];
+
+    // ---- Cholesky ----
+    for (int J = 0; J < nb; ++J) {
+        const int J0 = J * FB;
+        if (ib > J) {
+#pragma unroll
+            for (int c = 0; c < FB; ++c) acc[c] = row[J0 + c] / q.nm1;
+        } else if (ib == J) {
+#pragma unroll
+            for (int c = 0; c < FB; ++c) {
+                double v = c <= r ? row[J0 + c] / q.nm1 : 0.0;
+                if (c == r) v += q.eps;
+                acc[c] = v;
+            }
+        }
+        for (int K = 0; K < J; ++K) {
+            for (int e = i; e < FB * FB; e += nt) B[e >> 5][e & 31] = A[(int64_t)(J0 + (e >> 5)) * d + K * FB + (e & 31)];
+            __syncthreads();
+            if (ib >= J) {
+#pragma unroll
+                for (int k = 0; k < FB; ++k) l[k] = row[K * FB + k];
+                rank32(acc, l, B);
+            }
+            __syncthreads();
+        }
+        if (ib == J) {
+#pragma unroll
+            for (int c = 0; c < FB; ++c)
+                if (c <= r) Dg[r][c] = acc[c];
+        }
+        __syncthreads();
+        // the diagonal block, right-looking inside LDS: pivot, column, trailing update
+        for (int j = 0; j < FB; ++j) {
+            if (i == 0) {
+                const double piv = Dg[j][j];
+                if (piv > 0.0 && piv < __builtin_huge_val()) Dg[j][j] = sqrt(piv);
+                else fail = J0 + j + 1;          // LAPACK's info: a status, the workgroup leaves the loop below
+            }
+            __syncthreads();
+            if (fail) break;
+            if (i > j && i < FB) Dg[i][j] /= Dg[j][j];
+            __syncthreads();
+            for (int e = i; e < FB * FB; e += nt) {
+                const int rr = e >> 5, cc = e & 31;
+                if (cc > j && rr >= cc) Dg[rr][cc] = fma(-Dg[rr][j], Dg[cc][j], Dg[rr][cc]);
+            }
+            __syncthreads();
+        }
+        if (fail) break;
+        if (ib == J) {
+#pragma unroll
+            for (int c = 0; c < FB; ++c)
+                if (c <= r) row[J0 + c] = Dg[r][c];
+        } else if (ib > J) {
+#pragma unroll
+            for (int c = 0; c < FB; ++c) {
+                double s = acc[c];
+#pragma unroll
+                for (int k = 0; k < c; ++k) s = fma(-acc[k], Dg[c][k], s);
+                acc[c] = s / Dg[c][c];
+                row[J0 + c] = acc[c];
+            }
+        }
+        __syncthreads();
+    }
+    if (fail) {         // nothing a caller could take for a factor
+        if (i == 0) q.info[p] = fail;
+        const float nanf_ = __builtin_nanf("");
+        const double nan_ = __builtin_nan("");
+        for (int64_t e = i; e < dd; e += d) {
+            q.w[p * dd + e] = nanf_;
+            if (q.c_out) q.c_out[p * dd + e] = nan_;
+            if (q.w64_out) q.w64_out[p * dd + e] = nan_;
+        }
+        return;
+    }
+    if (q.c_out) {
+        for (int rr = 0; rr < d; ++rr) q.c_out[p * dd + (int64_t)rr * d + i] = i <= rr ? A[(int64_t)rr * d + i] : 0.0;
+        __syncthreads();
+    }
+
+    // ---- W = C^-1 ----
+    for (int J = 0; J < nb; ++J) {
+        const int J0 = J * FB;
+#pragma unroll
+        for (int c = 0; c < FB; ++c) acc[c] = 0.0;
+        for (int K = J; K < nb; ++K) {
+            const int K0 = K * FB;
+            if (ib == K) {
+#pragma unroll
+                for (int c = 0; c < FB; ++c) {
+                    if (c <= r) Dg[r][c] = row[K0 + c];
+                    Sb[r][c] = K == J ? (c == r ? 1.0 : 0.0) : acc[c];
+                }
+            }
+            __syncthreads();
+            if (i < FB) {       // column i of C[K][K]^-1 Sb
+                double x[FB];
+#pragma unroll
+                for (int rr = 0; rr < FB; ++rr) {
+                    double s = Sb[rr][i];
+#pragma unroll
+                    for (int qq = 0; qq < rr; ++qq) s = fma(-Dg[rr][qq], x[qq], s);
+                    x[rr] = s / Dg[rr][rr];
+                    B[i][rr] = x[rr];
+                }
+            }
+            __syncthreads();
+            if (ib == K) {
+#pragma unroll
+                for (int c = 0; c < FB; ++c)
+                    if (K > J || c <= r) row[J0 + c] = B[c][r];
+            } else if (ib > K) {
+#pragma unroll
+                for (int k = 0; k < FB; ++k) l[k] = row[K0 + k];
+                rank32(acc, l, B);
+            }
+            __syncthreads();
+        }
+    }
+    for (int rr = 0; rr < d; ++rr) {         // element (rr, i): coalesced, and only the lower triangle is read
+        const int64_t e = (int64_t)rr * d + i;
+        const bool low = i <= rr;
+        const double v = low ? A[e] : 0.0;
+        q.w[p * dd + e] = low ? (float)v : 0.f;
+        if (q.w64_out) q.w64_out[p * dd + e] = v;
+    }
+    if (i == 0) q.info[p] = 0;
+}
+
 }  // namespace
 
 // Per position p of the n_img images of x [n_img * P][D] (row n P + p), over the d columns sel[0..d): mean[p][k] and
@@ -261,6 +453,25 @@ extern "C" int ssad_position_gaussian_fit_stats(const float* x, const int* sel, 
     hipLaunchKernelGGL(padim_mean_kernel, dim3((unsigned)(P * cb)), dim3(64), 0, st, x, sel, mean, n_img, P, D, d);
     hipLaunchKernelGGL(padim_scatter_kernel, dim3((unsigned)(P * tiles)), dim3(256), 0, st, x, sel, (const double*)mean, scatter,
                        n_img, P, D, d, tiles);
+    SSAD_CHECK_LAUNCH();
+    return 0;
+}
+
+// Per position p: Sigma = scatter[p] / (n - 1) + eps I, C = its lower Cholesky factor, W = C^-1, all fp64 in place in the lower
+// triangle of scatter[p] (consumed; the upper triangle is neither read nor written); w = fp32(W) with +0 above the diagonal, mu_hi /
+// mu_lo the float pair of the mean, info[p] = 0 or 1 + the column of the first pivot that is not finite and positive (then w[p] is
+// all NaN).  One workgroup of d threads per position, fixed summation order: the same bits on every call and for every P.
+extern "C" int ssad_position_gaussian_factor(const double* mean, double* scatter, int64_t P, int d, int64_t n, double eps,
+                                             float* mu_hi, float* mu_lo, float* w, double* c_out, double* w64_out, int* info,
+                                             void* stream) {
+    SSAD_CHECK_ARG(mean && scatter && mu_hi && mu_lo && w && info, "null pointer");
+    SSAD_CHECK_ARG(d >= 32 && d % 32 == 0 && d <= FACTOR_MAX_D, "d must be a multiple of 32 in 32..512");
+    SSAD_CHECK_ARG(P >= 1 && P < (int64_t)2147483647, "need 1 <= P < 2^31");
+    SSAD_CHECK_ARG(n >= 2, "a covariance needs at least 2 images");
+    SSAD_CHECK_ARG(eps > 0.0, "eps must be positive");
+    SSAD_CHECK_ARG(((uintptr_t)mean | (uintptr_t)scatter | (uintptr_t)(c_out ? c_out : scatter) | (uintptr_t)(w64_out ? w64_out : scatter)) % 8 == 0, "fp64 buffers must be 8-byte aligned");
+    FactorParams q{mean, scatter, mu_hi, mu_lo, w, c_out, w64_out, info, d, (double)(n - 1), eps};
+    hipLaunchKernelGGL(position_factor_kernel, dim3((unsigned)P), dim3(d), 0, (hipStream_t)stream, q);
     SSAD_CHECK_LAUNCH();
     return 0;
 }

@@ -65,6 +65,8 @@ SIGNATURES = {
     "ssad_mahalanobis_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
     "ssad_position_gaussian_fit_stats": [_c_fp, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp],
     "ssad_position_mahalanobis": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_fp],
+    "ssad_position_gaussian_factor": [_c_fp, _c_fp, _c_l, _c_i, _c_l, ctypes.c_double, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp,
+                                      _c_fp],
     "ssad_blur_relu_bilinear": [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_flip_transpose_weight": [_c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_flip_transpose_batch": [_c_fp, _c_fp, ctypes.POINTER(ctypes.c_int64), _c_i, _c_fp],

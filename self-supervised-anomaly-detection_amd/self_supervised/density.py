@@ -210,10 +210,16 @@ class PositionGaussianDetector:
     fitted over the images, the Mahalanobis distance to it as the pixel score.  Rows are not L2-normalised.
 
     ``fit`` draws the 70/30 split over images (models.split_rows; `groups` given or implied by the row order), fits on the 70 % and
-    sets ``threshold`` to the largest score of the held-out images.  Patch level only, at least 2 fit images."""
+    sets ``threshold`` to the largest score of the held-out images.  Patch level only, at least 2 fit images.
+
+    ``factor``: where the P covariances are factored.  'host' (the default): ``position_gaussian_factor`` on copies of the statistics;
+    'device': ``ops.position_gaussian_factor``, a batched fp64 Cholesky + triangular inverse kernel on the statistics where they are
+    (channels <= 512) -- the fit never leaves the device."""
+
+    FACTORS = ('host', 'device')
 
     def __init__(self, patch_level: bool = True, batch: int = None, num_patches: int = None, channels: int = 96, eps: float = 0.01,
-                 seed: int = 0) -> None:
+                 seed: int = 0, factor: str = 'host') -> None:
         if not patch_level or not num_patches:
             raise ValueError("PositionGaussianDetector is a patch-level detector: patch_level=True and num_patches (positions per "
                              "image) are required")
@@ -221,6 +227,11 @@ class PositionGaussianDetector:
             raise ValueError(f"channels must be a multiple of 32, at least 32, got {channels!r}")
         if not eps > 0:
             raise ValueError(f"eps must be positive, got {eps!r}")
+        if not isinstance(factor, str) or factor not in self.FACTORS:
+            raise ValueError(f"factor must be one of {self.FACTORS}, got {factor!r}")
+        if factor == 'device' and channels > 512:
+            raise ValueError(f"factor='device' takes at most 512 channels, got {channels}")
+        self.factor = factor
         self.patch_level = True
         self.batch = batch
         self.num_patches = int(num_patches)
@@ -283,9 +294,13 @@ class PositionGaussianDetector:
         x = self._dev(bank)
         sel_dev = ops.position_sel(sel, x.shape[1], x.device)
         mean, scatter = ops.position_gaussian_fit_stats(x, sel, n_img, self.num_patches, sel_dev=sel_dev)
-        mu_hi, mu_lo, w = position_gaussian_factor(mean.cpu().numpy(), scatter.cpu().numpy(), n_img, self.eps)
+        if self.factor == 'device':
+            fitted = ops.position_gaussian_factor(mean, scatter, n_img, self.eps)       # consumes scatter; nothing visits the host
+        else:
+            fitted = position_gaussian_factor(mean.cpu().numpy(), scatter.cpu().numpy(), n_img, self.eps)
+            fitted = [torch.from_numpy(a).to(x.device) for a in fitted]
         self.sel, self._sel_dev = sel, sel_dev
-        self.mu_hi, self.mu_lo, self.w = (torch.from_numpy(a).to(x.device) for a in (mu_hi, mu_lo, w))
+        self.mu_hi, self.mu_lo, self.w = fitted
 
     def _scores(self, x):
         if self.w is None:
@@ -315,12 +330,12 @@ class PositionGaussianDetector:
     def state(self) -> dict:
         """What another rank needs to score (host tensors, picklable); the threshold travels beside it."""
         return {"sel": self.sel.cpu(), "mu_hi": self.mu_hi.cpu(), "mu_lo": self.mu_lo.cpu(), "w": self.w.cpu(), "eps": self.eps,
-                "channels": self.channels, "seed": self.seed}
+                "channels": self.channels, "seed": self.seed, "factor": self.factor}
 
     @classmethod
     def from_state(cls, state: dict, patch_level: bool = True, batch: int = None, num_patches: int = None):
         det = cls(patch_level=patch_level, batch=batch, num_patches=num_patches, channels=state["channels"], eps=state["eps"],
-                  seed=state.get("seed", 0))
+                  seed=state.get("seed", 0), factor=state.get("factor", "host"))
         det.mu_hi, det.mu_lo, det.w = (cls._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
         det.sel = torch.as_tensor(state["sel"]).cpu().long()
         det._sel_dev = ops.position_sel(det.sel, int(det.sel.max()) + 1, det.mu_hi.device)

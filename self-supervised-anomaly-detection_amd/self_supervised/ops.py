@@ -1028,6 +1028,36 @@ def position_gaussian_fit_stats(x, sel, n_img, P, sel_dev=None):
     return mean, scatter
 
 
+def position_gaussian_factor(mean, scatter, n, eps, want64=False):
+    """The per-position Gaussians in the form position_mahalanobis takes, on the device (csrc/padim.hip): mean [P][d], scatter
+    [P][d][d] fp64 device tensors of position_gaussian_fit_stats over n images -> (mu_hi [P][d], mu_lo [P][d], w [P][d][d]) fp32 with
+    Sigma_p = scatter_p / (n - 1) + eps I, C_p its lower Cholesky factor and w_p = C_p^-1 rounded once, exact zeros above the
+    diagonal; want64: also (c64, w64) [P][d][d] fp64, C and W before the rounding.  `scatter` is CONSUMED: it is the kernel's
+    workspace and holds W in its lower triangle afterwards.  Only its lower triangle is read.  ValueError naming the first position
+    and column whose pivot is not finite and positive (its rows of w are NaN).  FLOPs: 2 d^3 / 3 per position; bytes: the lower
+    triangle read and written once, w and the optional fp64 copies written once."""
+    f64 = torch.float64
+    if mean.dim() != 2 or tuple(scatter.shape) != (mean.shape[0], mean.shape[1], mean.shape[1]):
+        raise _hip.HipExtensionError(f"position_gaussian_factor: mean {tuple(mean.shape)} and scatter {tuple(scatter.shape)} are not "
+                                     f"[P][d] and [P][d][d]")
+    P, d = (int(v) for v in mean.shape)
+    mu_hi, mu_lo, w = _new((P, d), mean), _new((P, d), mean), _new((P, d, d), mean)
+    c64 = torch.empty((P, d, d), device=mean.device, dtype=f64) if want64 else None
+    w64 = torch.empty((P, d, d), device=mean.device, dtype=f64) if want64 else None
+    info = torch.empty((P,), device=mean.device, dtype=torch.int32)
+    _run("position_gaussian_factor", 2.0 * P * d ** 3 / 3, 8.0 * P * d * (d + 1) + 4.0 * P * d * d + (16.0 * P * d * d if want64 else 0.0),
+         lambda: _hip.lib().ssad_position_gaussian_factor(_hip.ptr(mean, dtype=f64), _hip.ptr(scatter, dtype=f64), P, d, int(n),
+                                                          float(eps), _hip.ptr(mu_hi), _hip.ptr(mu_lo), _hip.ptr(w),
+                                                          _hip.ptr(c64, True, f64), _hip.ptr(w64, True, f64),
+                                                          _hip.ptr(info, dtype=torch.int32), _hip.stream()))
+    bad = torch.nonzero(info)
+    if bad.numel():
+        p = int(bad[0])
+        raise ValueError(f"the covariance of position {p} is not positive definite: pivot {int(info[p]) - 1} is not finite and "
+                         f"positive ({int(bad.numel())} of {P} positions failed)")
+    return (mu_hi, mu_lo, w, c64, w64) if want64 else (mu_hi, mu_lo, w)
+
+
 def position_mahalanobis(x, sel, mu_hi, mu_lo, w, n_img, P, sel_dev=None, out=None):
     """x [n_img * P][D] fp32 -> [n_img * P] ||W_p (x[n P + p][sel] - mu_p)||_2 with mu = mu_hi + mu_lo ([P][d] fp32 pairs) and
     W [P][d][d] lower triangular, one kernel (csrc/padim.hip).  FLOPs: the dense 2 n P d^2 (the kernel skips W's zero blocks); bytes:

@@ -421,14 +421,14 @@ def _check_localization(localization, patch_localization):
     return localization
 
 
-PADIM_OPTIONS = ('channels', 'eps', 'seed')
+PADIM_OPTIONS = ('channels', 'eps', 'seed', 'factor')
 
 
 def _check_padim(detector, patch_localization, localization, bank, detector_options):
     """detector='padim' (PositionGaussianDetector) fits one Gaussian per map position over the training images: it needs
     positions that mean the same place in every image (patch_localization=True, localization='dense': one trunk pass per image) and
     more than one training image (bank='train': the reference's bank is ONE image, which gives no covariance).
-    `detector_options` (channels / eps / seed of the detector) belongs to 'padim' alone."""
+    `detector_options` (channels / eps / seed / factor of the detector) belongs to 'padim' alone."""
     if detector_options is not None:
         if detector != 'padim':
             raise ValueError(f"detector_options applies to detector='padim' only, got detector={detector!r}")
@@ -500,7 +500,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     same code.
     detector='padim' = one Gaussian per map position (PositionGaussianDetector: PaDiM; the Mahalanobis distance to the position's
     Gaussian over `channels` randomly chosen columns); needs patch_localization=True, localization='dense' and bank='train'; takes
-    image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed'} of that detector
+    image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed', 'factor'} of that detector
     ('padim' only).
     `metric`: 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's Euclidean distance between the raw rows
     (AnomalyDetector(metric='euclidean'): search, coreset selection and image scores all in that metric); 'knn' only."""

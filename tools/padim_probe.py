@@ -4,8 +4,13 @@ one loop, at the bottle-sized shape: P = 1024 positions, D = 384 columns, 146 fi
     beside a plain torch formulation on the same inputs (index_select of sel, centre, torch.bmm with W, norm);
 (b) the fit: the statistics kernel (event time), the host Cholesky + triangular inverse (wall time), the copies between them;
 with --inference, (c) the wall time of tools.inference(bank='train', localization='dense') on the synthetic 209 / 83-image category of
-§4.8 (seeded weights) with detector='padim' beside detector='knn', coreset=0.01, second round.
-   python tools/padim_probe.py [--inference]"""
+§4.8 (seeded weights) with detector='padim' beside detector='knn', coreset=0.01, second round;
+with --factor (instead of (a) and (b)), (d) the covariance factor on the statistics of (b): the device kernel
+(ops.position_gaussian_factor), the host path of the default (both copies, numpy Cholesky, torch triangular solve) and torch's own
+device routines (linalg.cholesky + solve_triangular against an explicit identity, on a Sigma formed beforehand) if this build has
+them, taking turns in one loop; then the wall time of tools.inference with factor='device' beside factor='host' at 96 and 384
+channels on the category of (c).
+   python tools/padim_probe.py [--inference] [--factor]"""
 import json
 import os
 import statistics
@@ -93,6 +98,86 @@ def kernels(d):
     print(json.dumps({"scoring": row}), flush=True)
 
 
+def factor(d, reps):
+    g = torch.Generator(device=dev).manual_seed(d)
+    base = torch.randn((1, P, D), device=dev, generator=g) * 2.0
+    fit = (base + torch.randn((N_FIT, P, D), device=dev, generator=g)).reshape(N_FIT * P, D).contiguous()
+    sel = position_channels(D, d, 0)
+    mean, scatter = ops.position_gaussian_fit_stats(fit, sel, N_FIT, P, sel_dev=ops.position_sel(sel, D, dev))
+    del fit
+    eps = 0.01
+    sigma = scatter / (N_FIT - 1) + eps * torch.eye(d, device=dev, dtype=torch.float64)
+    eye = torch.eye(d, device=dev, dtype=torch.float64).expand(P, d, d)
+    got = {}
+
+    def device(ws):
+        got["device"] = ops.position_gaussian_factor(mean, ws, N_FIT, eps)[2]
+
+    def host(ws):
+        mu_hi, mu_lo, w = position_gaussian_factor(mean.cpu().numpy(), ws.cpu().numpy(), N_FIT, eps)
+        got["host"] = [torch.from_numpy(a).to(dev) for a in (mu_hi, mu_lo, w)][2]
+
+    def torch_device(ws):
+        c = torch.linalg.cholesky(sigma)
+        got["torch"] = torch.linalg.solve_triangular(c, eye, upper=False).float()
+    fns = {"device": device, "host": host, "torch": torch_device}
+    row = {"d": d, "P": P, "images": N_FIT, "reps": reps}
+    try:
+        torch_device(None)
+        torch.cuda.synchronize()
+    except Exception as e:                                          # this torch build has no such routine on the device
+        row["torch"] = f"unavailable: {type(e).__name__}: {str(e)[:200]}"
+        del fns["torch"]
+    times = {k: [] for k in fns}
+    for rep in range(reps + 1):                                     # the first round warms up
+        for k, fn in fns.items():
+            ws = scatter.clone()                                    # the kernel consumes its input; the copy is not timed
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(ws)
+            e1.record()
+            e1.synchronize()
+            if rep:
+                times[k].append(e0.elapsed_time(e1))
+    for k, v in times.items():
+        row[k + "_ms"] = round(statistics.median(v), 3)
+    flops = 2.0 * P * d ** 3 / 3
+    row["device_fp64_GFLOPs"] = round(flops / row["device_ms"] / 1e6, 1)
+    row["host_over_device"] = round(row["host_ms"] / row["device_ms"], 1)
+    row["device_equals_host_w"] = bool(torch.equal(got["device"], got["host"]))
+    row["max_rel_diff_device_host_w"] = ((got["device"] - got["host"]).abs().max() / got["host"].abs().max()).item()
+    if "torch" in fns:
+        row["torch_fp64_GFLOPs"] = round(flops / row["torch_ms"] / 1e6, 1)
+    print(json.dumps({"factor": row}), flush=True)
+
+
+def factor_inference_wall():
+    from fake_mvtec import make_tree
+    from oracle import weights
+    from self_supervised import datasets, tools
+    tmp = tempfile.mkdtemp()
+    root = make_tree(os.path.join(tmp, "data"), categories=("bottle",), n_train=209, n_test_good=20, n_test_bad=63, size=256)
+    ck = os.path.join(tmp, "seeded.ckpt")
+    torch.save({"state_dict": weights.seeded_state_dict(0), "hyper_parameters": {}, "memory_bank": torch.tensor([])}, ck)
+    datasets._DataModule.num_workers = 0
+    out, maps = {}, {}
+    for _ in range(2):                                                # second round: warm caches
+        for ch in (96, 384):
+            for f in ("host", "device"):
+                np.random.seed(0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train',
+                                      localization='dense', detector='padim', detector_options={"channels": ch, "factor": f})
+                torch.cuda.synchronize()
+                out[f"padim_{ch}_{f}"] = round(time.perf_counter() - t0, 3)
+                maps[ch, f] = res.anomaly_maps
+    for ch in (96, 384):
+        out[f"padim_{ch}_max_rel_diff_of_maps"] = ((maps[ch, "device"] - maps[ch, "host"]).abs() / maps[ch, "host"]).max().item()
+    print(json.dumps({"factor_inference_wall_s": out, "bank": "train", "localization": "dense", "train_images": 209,
+                      "test_images": 83}), flush=True)
+
+
 def inference_wall():
     from fake_mvtec import make_tree
     from oracle import weights
@@ -123,6 +208,11 @@ def inference_wall():
 
 
 if __name__ == "__main__":
+    if "--factor" in sys.argv:
+        factor(96, 5)
+        factor(384, 3)
+        factor_inference_wall()
+        sys.exit(0)
     for d in (96, 384):
         kernels(d)
     if "--inference" in sys.argv:
