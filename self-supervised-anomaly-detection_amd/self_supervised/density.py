@@ -21,6 +21,7 @@ from scipy.linalg import solve_triangular
 from torch import Tensor
 
 from . import ops
+from .detectors import Detector
 
 
 def ledoit_wolf_covariance(mean, scatter, m4, n):
@@ -77,31 +78,19 @@ def ledoit_wolf_factor(mean, scatter, m4, n):
     return mu_hi, mu_lo, np.ascontiguousarray(w, dtype=np.float32), shrinkage
 
 
-class GaussianDensityDetector:
+class GaussianDensityDetector(Detector):
     """Opt-in second scorer with the call surface of ``models.AnomalyDetector``: a Ledoit-Wolf Gaussian fitted to the normal
     embeddings, the Mahalanobis distance to it as the score (CutPaste's GDE).
 
-    ``fit`` takes the same 70/30 split as ``AnomalyDetector.fit`` (models.split_indices: the same draws from the global numpy RNG,
+    ``fit`` takes the same 70/30 split as ``AnomalyDetector.fit`` (detectors.split_indices: the same draws from the global numpy RNG,
     quirk Q5), fits on the train part and sets ``threshold`` to the largest score of the held-out part.  Fitting needs at least
     2 rows: the image-level bank of ``tools.inference`` is ONE embedding (quirk Q3), so image-level GDE raises ValueError."""
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, normalize: bool = True) -> None:
-        self.patch_level = patch_level
-        self.batch = batch
-        self.dim = int(np.sqrt(num_patches)) if num_patches else None
+        super().__init__(patch_level, batch, num_patches)
         self.normalize = bool(normalize)
         self.mu_hi = self.mu_lo = self.w = None
         self.shrinkage = None
-        self.threshold = None
-
-    @staticmethod
-    def _dev(t):
-        t = torch.as_tensor(t, dtype=torch.float32)
-        if not t.is_cuda:
-            if not torch.cuda.is_available():
-                raise RuntimeError("GaussianDensityDetector needs the MI355X HIP kernels (no CPU fallback)")
-            t = t.cuda()
-        return t.contiguous()
 
     @staticmethod
     def fit_rows(n: int, split: bool = True) -> int:
@@ -112,20 +101,15 @@ class GaussianDensityDetector:
                              f"{', 70/30 split' if split else ''}); the image-level bank of tools.inference is one embedding")
         return m
 
-    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
-        """groups: image index per row -- the 70/30 split is then drawn over images (models.split_rows)."""
-        from .models import _take, split_rows
-        emb = torch.as_tensor(embeddings)
-        n = emb.shape[0]
+    def check_fit_size(self, rows: int, n_images, width: int) -> None:
+        if n_images is not None:        # the rows of the images the 70/30 split keeps
+            rows = (n_images - int(np.ceil(0.3 * n_images))) * (rows // max(1, n_images))
+        self.fit_rows(rows, split=n_images is None)
+
+    def _check_fit(self, emb, split, groups):
         if groups is None:
-            self.fit_rows(n, split)
-        if split:
-            train_idx, val_idx = split_rows(n, groups, 0.3)
-            train, val = _take(emb, train_idx), _take(emb, val_idx)
-        else:
-            train, val = emb, emb
-        self.fit_bank(train)
-        self.threshold = torch.max(self._scores(self._dev(val))).item()
+            self.fit_rows(int(emb.shape[0]), split)
+        return groups
 
     def fit_bank(self, bank: Tensor) -> None:
         n = int(torch.as_tensor(bank).shape[0])
@@ -138,22 +122,18 @@ class GaussianDensityDetector:
     def _scores(self, x):
         return ops.mahalanobis_fused(x, self.mu_hi, self.mu_lo, self.w, self.normalize)
 
-    def predict(self, x: Tensor) -> Tensor:
-        anomaly_scores = self._scores(self._dev(x))
-        if self.patch_level:
-            anomaly_scores = torch.reshape(anomaly_scores, (self.batch, 1, self.dim, self.dim))
-        return anomaly_scores
-
     def state(self) -> dict:
-        """What another rank needs to score (host tensors, picklable); the threshold travels beside it."""
         return {"mu_hi": self.mu_hi.cpu(), "mu_lo": self.mu_lo.cpu(), "w": self.w.cpu(), "shrinkage": self.shrinkage,
                 "normalize": self.normalize}
+
+    def load_state(self, state: dict) -> None:
+        self.mu_hi, self.mu_lo, self.w = (self._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
+        self.shrinkage, self.normalize = state["shrinkage"], state["normalize"]
 
     @classmethod
     def from_state(cls, state: dict, patch_level: bool = False, batch: int = None, num_patches: int = None):
         det = cls(patch_level=patch_level, batch=batch, num_patches=num_patches, normalize=state["normalize"])
-        det.mu_hi, det.mu_lo, det.w = (cls._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
-        det.shrinkage = state["shrinkage"]
+        det.load_state(state)
         return det
 
 
@@ -203,13 +183,13 @@ def position_gaussian_factor(mean, scatter, n, eps=0.01, chunk=64, dtype=np.floa
     return mu_hi, mu_lo, w
 
 
-class PositionGaussianDetector:
+class PositionGaussianDetector(Detector):
     """Opt-in third scorer (PaDiM, Defard et al., ICPR 2020, as anomalib implements it) with ``GaussianDensityDetector``'s call
     surface, for rows that are whole images of `num_patches` positions in (image, position) order (the dense rows of
     ``PeraNet.enable_dense_mode``): one Gaussian per position over `channels` randomly chosen columns (``position_channels``),
     fitted over the images, the Mahalanobis distance to it as the pixel score.  Rows are not L2-normalised.
 
-    ``fit`` draws the 70/30 split over images (models.split_rows; `groups` given or implied by the row order), fits on the 70 % and
+    ``fit`` draws the 70/30 split over images (detectors.split_rows; `groups` given or implied by the row order), fits on the 70 % and
     sets ``threshold`` to the largest score of the held-out images.  Patch level only, at least 2 fit images.
 
     ``factor``: where the P covariances are factored.  'host' (the default): ``position_gaussian_factor`` on copies of the statistics;
@@ -231,24 +211,12 @@ class PositionGaussianDetector:
             raise ValueError(f"factor must be one of {self.FACTORS}, got {factor!r}")
         if factor == 'device' and channels > 512:
             raise ValueError(f"factor='device' takes at most 512 channels, got {channels}")
+        super().__init__(True, batch, num_patches)
         self.factor = factor
-        self.patch_level = True
-        self.batch = batch
         self.num_patches = int(num_patches)
-        self.dim = int(np.sqrt(num_patches))
         self.channels, self.eps, self.seed = int(channels), float(eps), int(seed)
         self.sel = self.mu_hi = self.mu_lo = self.w = None
         self._sel_dev = None
-        self.threshold = None
-
-    @staticmethod
-    def _dev(t):
-        t = torch.as_tensor(t, dtype=torch.float32)
-        if not t.is_cuda:
-            if not torch.cuda.is_available():
-                raise RuntimeError("PositionGaussianDetector needs the MI355X HIP kernels (no CPU fallback)")
-            t = t.cuda()
-        return t.contiguous()
 
     @staticmethod
     def fit_images(n_img: int, split: bool = True) -> int:
@@ -264,27 +232,24 @@ class PositionGaussianDetector:
             raise ValueError(f"{rows} rows are not whole images of {self.num_patches} positions")
         return rows // self.num_patches
 
-    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
+    def check_fit_size(self, rows: int, n_images, width: int) -> None:
+        self.fit_images(self._images(rows) if n_images is None else n_images)      # the images the 70/30 split keeps
+        if self.channels > width:
+            raise ValueError(f"channels must be a multiple of 32 in 32..{width} (the rows' width), got {self.channels}")
+
+    def _check_fit(self, emb, split, groups):
         """groups: image index per row (default: implied by the row order, `num_patches` rows per image)."""
-        from .models import _take, split_rows
-        emb = torch.as_tensor(embeddings)
         n_img = self._images(int(emb.shape[0]))
         position_channels(int(emb.shape[1]), self.channels, self.seed)
         self.fit_images(n_img, split)
-        if split:
-            if groups is None:
-                groups = torch.arange(n_img).repeat_interleave(self.num_patches)
-            else:
-                g = torch.as_tensor(groups).cpu().reshape(-1).long()
-                if g.numel() != emb.shape[0] or not torch.equal(torch.bincount(g, minlength=n_img),
-                                                                torch.full((n_img,), self.num_patches)):
-                    raise ValueError(f"groups must give every one of the {n_img} images {self.num_patches} rows")
-            train_idx, val_idx = split_rows(int(emb.shape[0]), groups, 0.3)
-            train, val = _take(emb, train_idx), _take(emb, val_idx)
-        else:
-            train, val = emb, emb
-        self.fit_bank(train)
-        self.threshold = torch.max(self._scores(self._dev(val))).item()
+        if not split:
+            return groups
+        if groups is None:
+            return torch.arange(n_img).repeat_interleave(self.num_patches)
+        g = torch.as_tensor(groups).cpu().reshape(-1).long()
+        if g.numel() != emb.shape[0] or not torch.equal(torch.bincount(g, minlength=n_img), torch.full((n_img,), self.num_patches)):
+            raise ValueError(f"groups must give every one of the {n_img} images {self.num_patches} rows")
+        return groups
 
     def fit_bank(self, bank: Tensor) -> None:
         bank = torch.as_tensor(bank)
@@ -310,33 +275,26 @@ class PositionGaussianDetector:
             raise ValueError(f"the rows have {x.shape[1]} columns, the fitted selection reaches column {int(self.sel.max())}")
         return ops.position_mahalanobis(x, self.sel, self.mu_hi, self.mu_lo, self.w, n_img, self.num_patches, sel_dev=self._sel_dev)
 
-    def predict(self, x: Tensor) -> Tensor:
-        s = self._scores(self._dev(x))
-        return torch.reshape(s, (s.shape[0] // self.num_patches if self.batch is None else self.batch, 1, self.dim, self.dim))
-
-    def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = None, scores: Tensor = None) -> Tensor:
-        """PaDiM's image score: the largest patch score of every image (ops.rows_argmax).  x [batch * P][D]; `scores`: the map
-        predict returned, when the caller has it already.  'reweighted' needs a nearest bank row, which a Gaussian has not;
-        `neighbours` belongs to that mode and is accepted for AnomalyDetector's call surface only."""
-        if mode != 'max':
+    def _check_image_scores(self, mode, neighbours) -> None:
+        if mode != 'max':               # (`neighbours` belongs to 'reweighted': accepted for AnomalyDetector's call surface only)
             raise ValueError(f"PositionGaussianDetector.image_scores: mode must be 'max' (a Gaussian patch score has no nearest bank "
                              f"row to reweight with), got {mode!r}")
-        x = self._dev(x)
-        n_img = self._images(int(x.shape[0]))
-        s = self._scores(x) if scores is None else self._dev(scores)
-        smax, _ = ops.rows_argmax(s.reshape(n_img, self.num_patches))
-        return smax
+
+    def _image_patches(self, rows: int) -> int:
+        return self._images(rows) and self.num_patches
 
     def state(self) -> dict:
-        """What another rank needs to score (host tensors, picklable); the threshold travels beside it."""
         return {"sel": self.sel.cpu(), "mu_hi": self.mu_hi.cpu(), "mu_lo": self.mu_lo.cpu(), "w": self.w.cpu(), "eps": self.eps,
                 "channels": self.channels, "seed": self.seed, "factor": self.factor}
+
+    def load_state(self, state: dict) -> None:
+        self.mu_hi, self.mu_lo, self.w = (self._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
+        self.sel = torch.as_tensor(state["sel"]).cpu().long()
+        self._sel_dev = ops.position_sel(self.sel, int(self.sel.max()) + 1, self.mu_hi.device)
 
     @classmethod
     def from_state(cls, state: dict, patch_level: bool = True, batch: int = None, num_patches: int = None):
         det = cls(patch_level=patch_level, batch=batch, num_patches=num_patches, channels=state["channels"], eps=state["eps"],
                   seed=state.get("seed", 0), factor=state.get("factor", "host"))
-        det.mu_hi, det.mu_lo, det.w = (cls._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
-        det.sel = torch.as_tensor(state["sel"]).cpu().long()
-        det._sel_dev = ops.position_sel(det.sel, int(det.sel.max()) + 1, det.mu_hi.device)
+        det.load_state(state)
         return det

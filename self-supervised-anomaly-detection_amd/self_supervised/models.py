@@ -15,6 +15,8 @@ from torch import Tensor, nn
 from . import engine, ops
 from .constants import ModelOutputsContainer
 from .converters import gt2label, multiclass2binary
+from .density import GaussianDensityDetector, PositionGaussianDetector  # noqa: F401  (re-exported)
+from .detectors import Detector, _take, split_indices, split_rows  # noqa: F401  (re-exported)
 from .functional import get_prediction_class
 
 try:                                    # optional: behave as a LightningModule when PL is installed
@@ -381,37 +383,6 @@ class PeraNet(_Base):
         return [optimizer], []
 
 
-def split_indices(n, test_size=0.3):
-    """Index form of sklearn.model_selection.train_test_split(test_size=..., random_state=None, shuffle=True):
-    n_test = ceil(test_size*n); one permutation from the global numpy RNG; test = its first n_test entries,
-    train = the rest (quirk Q5: unseeded in the reference)."""
-    n_test = int(np.ceil(test_size * n))
-    perm = np.random.permutation(n)
-    return perm[n_test:], perm[:n_test]
-
-
-def split_rows(n, groups=None, test_size=0.3):
-    """(train, held-out) row indices of the detectors' 70/30 split.  groups=None: split_indices(n) over the rows.  groups [n] (the
-    image index 0..G-1 of every row): the split is drawn over the IMAGES -- split_indices(G), one permutation from the global numpy
-    RNG -- and every row goes with its image, images in the permutation's order, rows ascending within an image.  (A row split would
-    put overlapping patches of one image on both sides and drive the threshold towards 0.)"""
-    if groups is None:
-        return split_indices(n, test_size)
-    g = np.asarray(torch.as_tensor(groups).cpu()).reshape(-1).astype(np.int64)
-    if g.shape[0] != n:
-        raise ValueError(f"groups has {g.shape[0]} entries for {n} rows")
-    order = np.argsort(g, kind="stable")
-    n_groups = int(g.max()) + 1 if n else 0
-    bounds = np.searchsorted(g[order], np.arange(n_groups + 1))
-    tr, va = split_indices(n_groups, test_size)
-    take = lambda ids: (np.concatenate([order[bounds[i]:bounds[i + 1]] for i in ids]) if len(ids) else np.zeros(0, np.int64))
-    return take(tr), take(va)
-
-
-def _take(t, idx):
-    return t[torch.as_tensor(idx, dtype=torch.int64, device=t.device)]
-
-
 CORESET_SEED = 20230611   # seed of the coreset projection's own CPU generator
 _CORESET_OMEGA = {}
 
@@ -488,7 +459,7 @@ def coreset_select(bank_n, m, coreset_dim=128):
     return ops.coreset_greedy(p, m, start=0)
 
 
-class AnomalyDetector:
+class AnomalyDetector(Detector):
     """src/self_supervised/models.py:345-370: cosine 3-NN distance to a bank of normal embeddings.
 
     ``fit`` keeps the reference's unseeded 70/30 split (quirk Q5: depends on the global numpy RNG);
@@ -505,39 +476,18 @@ class AnomalyDetector:
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
                  coreset_dim: int = 128, metric: str = 'cosine') -> None:
-        self.patch_level = patch_level
-        self.batch = batch
-        self.dim = int(np.sqrt(num_patches)) if num_patches else None
+        super().__init__(patch_level, batch, num_patches)
         self.k = 3
         self.bank = None
         self.bank_sq = None             # metric='euclidean': squared norms of the bank rows (ops.row_sqnorms)
         self.metric = check_metric(metric)
-        self.threshold = None
         self.coreset = check_coreset(coreset, coreset_dim)
         self.coreset_dim = coreset_dim
         self.coreset_rows = None        # after fit with a coreset: (sel, rad) -- sel indexes the bank rows after the split
         self.coreset_counts = None      # after fit with a coreset: (rows kept, rows after the split)
 
-    @staticmethod
-    def _dev(t):
-        t = torch.as_tensor(t, dtype=torch.float32)
-        if not t.is_cuda:
-            if not torch.cuda.is_available():
-                raise RuntimeError("AnomalyDetector needs the MI355X HIP kernels (no CPU fallback)")
-            t = t.cuda()
-        return t.contiguous()
-
-    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
-        """groups: image index per row -- the 70/30 split is then drawn over images (split_rows)."""
-        emb = torch.as_tensor(embeddings)
-        n = emb.shape[0]
-        if split:
-            train_idx, val_idx = split_rows(n, groups, 0.3)
-            train, val = _take(emb, train_idx), _take(emb, val_idx)
-        else:
-            train, val = emb, emb
-        self.k = 3
-        self.fit_bank(train)
+    def _after_bank(self) -> None:
+        self.k = 3                      # as the reference's fit sets it; read by _scores for the threshold
         if self.coreset is not None:
             r = int(self.bank.shape[0])
             m = coreset_size(self.coreset, r)
@@ -548,8 +498,9 @@ class AnomalyDetector:
                     self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
                 self.coreset_rows = (sel, rad)
             self.coreset_counts = (int(self.bank.shape[0]), r)
-        scores = self._scores(self._dev(val))
-        self.threshold = torch.max(scores).item()
+
+    def describe_fit(self):
+        return None if self.coreset_counts is None else f' coreset: {self.coreset_counts[0]} of {self.coreset_counts[1]} rows'
 
     def _check_width(self, what, d):
         if d % 32:
@@ -589,12 +540,6 @@ class AnomalyDetector:
             out[i:i + step] = ops.cosine_knn_mean(sim, self.k)
         return out
 
-    def predict(self, x: Tensor) -> Tensor:
-        anomaly_scores = self._scores(self._dev(x))
-        if self.patch_level:
-            anomaly_scores = torch.reshape(anomaly_scores, (self.batch, 1, self.dim, self.dim))
-        return anomaly_scores
-
     def kneighbors(self, x: Tensor, k: int = None):
         """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
         idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by the detector's metric, nearest first, equal
@@ -610,26 +555,21 @@ class AnomalyDetector:
             dist, idx = ops.cosine_knn_index(x, self.bank, self.k if k is None else k)
         return dist, idx.long()
 
-    def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = 9, scores: Tensor = None) -> Tensor:
-        """One score per image from the patch scores (patch level only; PatchCore eq. 6-7 with the detector's metric).  x [batch * P][D]
-        patch embeddings, image after image.  s_p = the patch scores predict returns (`scores`: that map, when the caller has it
-        already); p* = argmax_p s_p, the smallest p on ties.
-        'max': s_{p*}.  'reweighted': w s_{p*}, w = 1 - exp(d(x_{p*}, m*)) / sum_{r in N} exp(d(x_{p*}, r)) with m* the nearest
-        bank row of x_{p*} and N the min(neighbours, R) bank rows nearest to B_{m*} (2 <= neighbours <= 32).  Returns [batch]."""
+    def _check_image_scores(self, mode, neighbours) -> None:
         check_image_scores(mode, neighbours)
         if not self.patch_level or not self.dim:
             raise ValueError("image_scores needs a patch-level detector (patch_level=True with num_patches)")
         if self.bank is None:
             raise ValueError("image_scores: the detector has no bank (fit or fit_bank first)")
-        x = self._dev(x)
-        p = self.dim * self.dim
-        if x.shape[0] % p:
-            raise ValueError(f"image_scores: {x.shape[0]} rows are not whole images of {p} patches")
-        s = self._scores(x) if scores is None else self._dev(scores)
-        smax, flat = ops.rows_argmax(s.reshape(x.shape[0] // p, p))
-        if mode == 'max':
-            return smax
-        xs = x.index_select(0, flat)                                     # x_{p*} of every image
+
+    def _image_patches(self, rows: int) -> int:
+        if rows % self.dim ** 2:
+            raise ValueError(f"image_scores: {rows} rows are not whole images of {self.dim ** 2} patches")
+        return self.dim ** 2
+
+    def _reweight(self, xs, smax, neighbours):
+        """image_scores(mode='reweighted') (PatchCore eq. 6-7 with the detector's metric): w s_{p*}, w = 1 - exp(d(x_{p*}, m*)) /
+        sum_{r in N} exp(d(x_{p*}, r)), m* the nearest bank row of x_{p*} (`xs`), N the min(neighbours, R) bank rows nearest to B_{m*}."""
         if self.metric == 'euclidean':
             _, mstar = ops.l2_knn_index(xs, self.bank, self.bank_sq, 1)
             rows = mstar.reshape(-1).long()
@@ -644,5 +584,4 @@ class AnomalyDetector:
         return ops.knn_reweight(xs, self.bank, mstar, nbr, smax)
 
 
-from .density import GaussianDensityDetector  # noqa: E402,F401  (opt-in second scorer: Ledoit-Wolf Gaussian, Mahalanobis distance)
-from .density import PositionGaussianDetector  # noqa: E402,F401  (opt-in third scorer: PaDiM, one Gaussian per map position)
+DETECTORS = {'knn': AnomalyDetector, 'gde': GaussianDensityDetector, 'padim': PositionGaussianDetector}     # tools.inference(detector=...)

@@ -8,6 +8,7 @@ import json
 import os
 import random
 import shutil
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -17,8 +18,8 @@ from . import metrics as mtr
 from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
-from .models import (AnomalyDetector, GaussianDensityDetector, PeraNet, PositionGaussianDetector, check_coreset,
-                     check_image_scores, check_metric)
+from . import models
+from .models import PeraNet, PositionGaussianDetector, check_coreset, check_image_scores, check_metric
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -355,7 +356,7 @@ def _mark(name):
         TIMELINE.append((name, time.perf_counter()))
 
 
-DETECTORS = ('knn', 'gde', 'padim')
+DETECTORS = tuple(models.DETECTORS)     # ('knn', 'gde', 'padim'): the names; models.DETECTORS maps them to the classes
 
 
 def _check_detector(detector):
@@ -447,10 +448,20 @@ def _check_padim(detector, patch_localization, localization, bank, detector_opti
     return opts
 
 
-def _print_coreset(detector):
-    counts = getattr(detector, "coreset_counts", None)
-    if counts is not None:
-        print(f' coreset: {counts[0]} of {counts[1]} rows')
+def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options):
+    """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
+    _check_detector(detector)
+    _check_metric(metric, detector)
+    _check_localization(localization, patch_localization)
+    _check_bank(bank, mvtec_inference)
+    _check_coreset(coreset, detector)
+    _check_image_scores(image_scores, neighbours, patch_localization, detector)
+    det_kw = _check_padim(detector, patch_localization, localization, bank, options)
+    if coreset is not None:
+        det_kw["coreset"] = coreset
+    if metric != 'cosine':
+        det_kw["metric"] = metric
+    return models.DETECTORS[detector], det_kw
 
 
 def _embed_files(model, tester, dataset, files):
@@ -479,46 +490,13 @@ def _train_bank_rows(per_image, n_total, device):
     return rows.contiguous(), groups
 
 
-def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
-              patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
-              coreset=None, image_scores: str = None, neighbours: int = 9,
-              localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine') -> ModelOutputsContainer:
-    """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
-    estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
-    `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
-    (quirks Q3 / Q4), so image-level 'gde' raises.  'train' = every image of train/good in file order (one row per image at image
-    level, its patches at patch level), the 70/30 split drawn over images; MVTec data only.
-    `coreset`: None (default) = the kNN bank keeps every row; a fraction in (0, 1] or an int >= 1 = a greedy k-center coreset of
-    that many of the bank rows left after the split (AnomalyDetector(coreset=...)); 'knn' only.
-    `image_scores`: None (default) = maps only, as the reference; 'max' / 'reweighted' = the container also carries
-    `image_scores` [n_images] (test-set file order): the largest raw patch score of every image, for 'reweighted' weighted by the
-    `neighbours` (2..32, default 9) bank rows around its nearest bank row (AnomalyDetector.image_scores; PatchCore eq. 6-7).  Needs
-    patch_localization=True and detector='knn'; the maps are unchanged.
-    `localization`: how patch_localization=True gets its rows.  'patches' (default) = the reference's 32 x 32 windows at stride 8, one
-    trunk pass per window (29 x 29 maps for 256 x 256 images); 'dense' = one trunk pass per image, rows = the locally aware patch
-    features of the layer2 and layer3 maps (PeraNet.enable_dense_mode: 32 x 32 maps, 384 columns); everything after the rows is the
-    same code.
-    detector='padim' = one Gaussian per map position (PositionGaussianDetector: PaDiM; the Mahalanobis distance to the position's
-    Gaussian over `channels` randomly chosen columns); needs patch_localization=True, localization='dense' and bank='train'; takes
-    image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed', 'factor'} of that detector
-    ('padim' only).
-    `metric`: 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's Euclidean distance between the raw rows
-    (AnomalyDetector(metric='euclidean'): search, coreset selection and image scores all in that metric); 'knn' only."""
-    scorer = _check_detector(detector)
-    _check_metric(metric, scorer)
-    _check_localization(localization, patch_localization)
-    _check_bank(bank, mvtec_inference)
-    _check_coreset(coreset, scorer)
-    _check_image_scores(image_scores, neighbours, patch_localization, scorer)
-    padim_kw = _check_padim(scorer, patch_localization, localization, bank, detector_options)
-    whole = bank == 'train'
-    del TIMELINE[:]
-    print('>>> initializing inference')
+def _plan_inputs(dataset_dir, mvtec_inference, whole):
+    """What `inference` reads: the datamodule, this rank's share of the test images (`mine`) and, with bank='train', of the training
+    images (`my_train` of `train_files`), else the ONE training image the bank comes from (`bank_file` / `bank_item`); the decode threads."""
     # MVTec test data: file lists and decode threads start BEFORE the checkpoint is read, so that the first group of images is
     # decoded by the time the model is on the device (the datamodule draws nothing from the global generators)
     rank, world = world_info()
-    datamodule = prefetch = mine = None
-    bank_file = bank_item = None
+    datamodule = prefetch = mine = bank_file = bank_item = train_files = my_train = None
     if mvtec_inference:
         datamodule = MVTecDatamodule(dataset_dir, batch_size=1)
         datamodule.setup('predict')
@@ -554,8 +532,11 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
                 bank_file = None
             # (a rank without test images of its own -- more ranks than images -- scores nothing, the bank image included)
             prefetch = _MVTecPrefetch(datamodule.test_dataset, mine, extra_files=[bank_file] if (bank_file and mine) else ())
-    print('>>> preparing model')
-    _mark("prefetch-started")
+    return SimpleNamespace(rank=rank, world=world, datamodule=datamodule, prefetch=prefetch, mine=mine, bank_file=bank_file,
+                           bank_item=bank_item, train_files=train_files, my_train=my_train)
+
+
+def _load_model(model_input_dir, patch_localization, localization, prefetch):
     try:
         model = PeraNet.load_from_checkpoint(model_input_dir)
         _mark("checkpoint")
@@ -569,125 +550,98 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         if prefetch is not None:               # no model, no predict: the decode threads are not left behind
             prefetch.close(cancel=True)
         raise
-    print('>>> preparing datamodule')
-    if mvtec_inference:
-        model.enable_mvtec_inference()
-    else:
-        datamodule = PretextTaskDatamodule(subject=subject, root_dir=dataset_dir, min_dataset_length=500, batch_size=1)
-    print('>>> doing prediction')
+    return model, tester
+
+
+def _predict(model, tester, datamodule, plan):
+    """-> (output container, the embeddings where they stayed on the device else None, images this rank predicted)."""
     # under torch.distributed (one process per GPU) every rank scores its own round-robin share of the images; the
     # per-image containers are exchanged once at the end so that every rank returns the full output
-    emb_dev = None
-    if prefetch is not None:
+    if plan.prefetch is not None:
         # the hot path of an evaluation: one stream through decode threads and large launches instead of a DataLoader of batch
         # size 1 (same values; _predict_mvtec_streamed).  The DataLoader iterator the reference creates here draws its base
         # seed from torch's global generator: the draw is kept, so that what follows (the shuffled loader of the normality
         # image) sees the same generator state
-        if bank_file is None and not whole:
+        if plan.bank_file is None and plan.train_files is None:
             torch.empty((), dtype=torch.int64).random_()
         model.to(tester.device).eval()
         _mark("model-on-device")
-        output, emb_dev = _predict_mvtec_streamed(model, datamodule.test_dataset, tester.device, mine, prefetch=prefetch)
+        output, emb_dev = _predict_mvtec_streamed(model, datamodule.test_dataset, tester.device, plan.mine, prefetch=plan.prefetch)
         _mark("predicted")
-        n_pred = len(mine)
-    else:
-        predictions = tester.predict(model, datamodule=datamodule, shard=world > 1)
-        output = ModelOutputsContainer()
-        output.from_list(predictions)
-        n_pred = len(predictions)
-    print('>>> anomaly detection phase')
-    groups = None
-    kind = {'gde': GaussianDensityDetector, 'padim': PositionGaussianDetector}.get(scorer, AnomalyDetector)
-    det_kw = dict(padim_kw) if scorer == 'padim' else ({} if coreset is None else {"coreset": coreset})
-    if metric != 'cosine':
-        det_kw["metric"] = metric
-    if patch_localization:
-        detector = kind(patch_level=True, batch=n_pred, num_patches=model.num_patches, **det_kw)
-    else:
-        detector = kind(**det_kw)
-    if whole:
+        return output, emb_dev, len(plan.mine)
+    predictions = tester.predict(model, datamodule=datamodule, shard=plan.world > 1)
+    output = ModelOutputsContainer()
+    output.from_list(predictions)
+    return output, None, len(predictions)
+
+
+def _normality_rows(model, tester, output, plan, dataset_dir, subject, mvtec_inference):
+    """-> (normality, groups): the rows the detector is fitted on, and with bank='train' the image index of every row (else None)."""
+    if plan.train_files is not None:
         # the training images' embeddings: from the stream (in front of the test images) or, with the streamed predict off or no test
         # images on this rank, from Trainer.predict over an unshuffled loader -- the same rows either way
         extra = getattr(output, "extra_embeddings", None)
         if extra is not None:
-            p_img = extra.shape[0] // len(my_train)
-            mine_train = [extra[j * p_img:(j + 1) * p_img] for j in range(len(my_train))]
+            p_img = extra.shape[0] // len(plan.my_train)
+            mine_train = [extra[j * p_img:(j + 1) * p_img] for j in range(len(plan.my_train))]
             del output.extra_embeddings
         else:
-            mine_train = _embed_files(model, tester, datamodule.test_dataset, my_train)
-        print(f' fitting on the whole training set ({len(train_files)} images)')
-        normality, groups = _train_bank_rows(mine_train, len(train_files), tester.device)
+            mine_train = _embed_files(model, tester, plan.datamodule.test_dataset, plan.my_train)
+        print(f' fitting on the whole training set ({len(plan.train_files)} images)')
+        normality, groups = _train_bank_rows(mine_train, len(plan.train_files), tester.device)
         _mark("train-bank")
-    elif model.memory_bank.shape[0] > 1000:            # quirk Q3: the bank is capped at 1000 rows, so this never holds
-        normality = model.memory_bank
-    elif bank_file is not None and getattr(output, "extra_embeddings", None) is not None:
-        print(' not enough data in memory bank, sampling new data trom train set')
-        normality = output.extra_embeddings.cpu()       # the training image scored in front of the test images (see above)
+        return normality, groups
+    if model.memory_bank.shape[0] > 1000:              # quirk Q3: the bank is capped at 1000 rows, so this never holds
+        return model.memory_bank, None
+    print(' not enough data in memory bank, sampling new data trom train set')
+    if plan.bank_file is not None and getattr(output, "extra_embeddings", None) is not None:
+        normality = output.extra_embeddings.cpu()       # the training image scored in front of the test images (_plan_inputs)
         del output.extra_embeddings
-    elif bank_item is not None:
+        return normality, None
+    if plan.bank_item is not None:
         # the draws are made and the image is known, but it did not ride with test images (a rank that has none): score that very
         # image -- drawing again would pick another one
-        print(' not enough data in memory bank, sampling new data trom train set')
-        ds_, i_ = bank_item
+        ds_, i_ = plan.bank_item
         model.to(tester.device).eval()
         with torch.no_grad():
             one = model.predict_step(tuple(t.unsqueeze(0).to(tester.device) for t in ds_[i_]), 0)
         one.to_cpu()
-        normality = one.embedding_vectors
+        return one.embedding_vectors, None
+    if mvtec_inference:
+        normality_datamodule = MVTecDatamodule(dataset_dir, batch_size=1)
+        normality_datamodule.num_workers = 0      # one deterministic image is read: not worth eight worker processes
     else:
-        print(' not enough data in memory bank, sampling new data trom train set')
-        if mvtec_inference:
-            normality_datamodule = MVTecDatamodule(dataset_dir, batch_size=1)
-        else:
-            normality_datamodule = PretextTaskDatamodule(subject=subject, root_dir=dataset_dir, batch_size=1)
-        if mvtec_inference:
-            normality_datamodule.num_workers = 0      # one deterministic image is read: not worth eight worker processes
-        normality_datamodule.setup()
-        # the reference predicts the WHOLE training loader and keeps element [0] (tools.py:379-381); the first batch of a loader
-        # does not depend on how far the loader is consumed afterwards (the shuffle permutation and the one draw for the workers'
-        # base seed happen when iteration starts), so only that batch is predicted: same image, same RNG state, 1 / 209 of the work
-        # (MVTec loader only: its __getitem__ draws no random numbers, so this also holds with in-process loading)
-        output_normality = tester.predict(model, dataloaders=normality_datamodule.train_dataloader(),
-                                          max_batches=1 if mvtec_inference else None)[0]
-        output_normality.to_cpu()
-        normality = output_normality.embedding_vectors
-    output.to_cpu()
-    if scorer == 'gde' and groups is not None:
-        # on every rank, before anybody waits for a broadcast: the rows of the images the 70/30 split keeps
-        n_img = len(train_files)
-        GaussianDensityDetector.fit_rows((n_img - int(np.ceil(0.3 * n_img))) * (int(normality.shape[0]) // max(1, n_img)), split=False)
-    elif scorer == 'gde':
-        GaussianDensityDetector.fit_rows(int(normality.shape[0]))      # on every rank, before anybody waits for a broadcast
-    elif scorer == 'padim':
-        # on every rank, before anybody waits for a broadcast: the images the 70/30 split keeps, and the channel count
-        PositionGaussianDetector.fit_images(len(train_files))
-        if detector.channels > int(normality.shape[1]):
-            raise ValueError(f"channels must be a multiple of 32 in 32..{int(normality.shape[1])} (the rows' width), got "
-                             f"{detector.channels}")
-    fit_kw = {} if groups is None else {"groups": groups}      # (the default bank: the reference's fit call, unchanged)
-    if world > 1:
-        # one bank for everybody: rank 0 draws the 70/30 split and fits, the others receive (bank, threshold) -- (state, threshold)
-        # of the Gaussian for 'gde'
-        if rank == 0:
-            detector.fit(normality, **fit_kw)
-            _print_coreset(detector)
-            payload = (detector.state(), detector.threshold)
-        state = broadcast_bank(payload if rank == 0 else None)
-        if rank != 0:
-            if scorer == 'gde':
-                detector = GaussianDensityDetector.from_state(state[0], patch_level=detector.patch_level, batch=detector.batch,
-                                                              num_patches=detector.dim ** 2 if detector.dim else None)
-                detector.threshold = state[1]
-            elif scorer == 'padim':
-                detector = PositionGaussianDetector.from_state(state[0], batch=detector.batch, num_patches=detector.num_patches)
-                detector.threshold = state[1]
-            else:
-                detector.load_state(state[0])         # the bank carries its metric; bank_sq is recomputed here, the same bits
-                detector.threshold = state[1]
-    else:
-        detector.fit(normality, **fit_kw)
-        _print_coreset(detector)
-    _mark("bank-fitted")
+        normality_datamodule = PretextTaskDatamodule(subject=subject, root_dir=dataset_dir, batch_size=1)
+    normality_datamodule.setup()
+    # the reference predicts the WHOLE training loader and keeps element [0] (tools.py:379-381); the first batch of a loader
+    # does not depend on how far the loader is consumed afterwards (the shuffle permutation and the one draw for the workers'
+    # base seed happen when iteration starts), so only that batch is predicted: same image, same RNG state, 1 / 209 of the work
+    # (MVTec loader only: its __getitem__ draws no random numbers, so this also holds with in-process loading)
+    output_normality = tester.predict(model, dataloaders=normality_datamodule.train_dataloader(),
+                                      max_batches=1 if mvtec_inference else None)[0]
+    output_normality.to_cpu()
+    return output_normality.embedding_vectors, None
+
+
+def _fit_or_receive(detector, normality, groups, plan):
+    # on every rank, before anybody waits for a broadcast
+    detector.check_fit_size(int(normality.shape[0]), None if groups is None else len(plan.train_files), int(normality.shape[1]))
+    if plan.world > 1 and plan.rank != 0:
+        # one bank for everybody: rank 0 draws the 70/30 split and fits, the others receive (state, threshold); a kNN bank carries its
+        # metric, and what load_state derives from the state (bank_sq) it recomputes with the same kernel: the same bits
+        state = broadcast_bank(None)
+        detector.load_state(state[0])
+        detector.threshold = state[1]
+        return
+    detector.fit(normality, **({} if groups is None else {"groups": groups}))      # (the default bank: the reference's fit call, unchanged)
+    line = detector.describe_fit()
+    if line:
+        print(line)
+    if plan.world > 1:
+        broadcast_bank((detector.state(), detector.threshold))
+
+
+def _score_and_gather(detector, output, emb_dev, n_pred, image_scores, neighbours, world, datamodule):
     print(' computing anomaly scores')
     scored = emb_dev if emb_dev is not None else output.embedding_vectors
     maps = detector.predict(scored)
@@ -698,11 +652,60 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
         output.image_scores = detector.image_scores(scored, image_scores, neighbours, scores=maps.reshape(-1)).cpu()
         _mark("image-scores")
     if world > 1:
-        n_total = len(datamodule.test_dataset)
-        per_image = gather_in_order(_split_container(output, n_pred), n_total)
+        per_image = gather_in_order(_split_container(output, n_pred), len(datamodule.test_dataset))
         output = ModelOutputsContainer()
         output.from_list(per_image)
     return output
+
+
+def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
+              patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
+              coreset=None, image_scores: str = None, neighbours: int = 9,
+              localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine') -> ModelOutputsContainer:
+    """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
+    estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
+    `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
+    (quirks Q3 / Q4), so image-level 'gde' raises.  'train' = every image of train/good in file order (one row per image at image
+    level, its patches at patch level), the 70/30 split drawn over images; MVTec data only.
+    `coreset`: None (default) = the kNN bank keeps every row; a fraction in (0, 1] or an int >= 1 = a greedy k-center coreset of
+    that many of the bank rows left after the split (AnomalyDetector(coreset=...)); 'knn' only.
+    `image_scores`: None (default) = maps only, as the reference; 'max' / 'reweighted' = the container also carries
+    `image_scores` [n_images] (test-set file order): the largest raw patch score of every image, for 'reweighted' weighted by the
+    `neighbours` (2..32, default 9) bank rows around its nearest bank row (AnomalyDetector.image_scores; PatchCore eq. 6-7).  Needs
+    patch_localization=True and detector='knn'; the maps are unchanged.
+    `localization`: how patch_localization=True gets its rows.  'patches' (default) = the reference's 32 x 32 windows at stride 8, one
+    trunk pass per window (29 x 29 maps for 256 x 256 images); 'dense' = one trunk pass per image, rows = the locally aware patch
+    features of the layer2 and layer3 maps (PeraNet.enable_dense_mode: 32 x 32 maps, 384 columns); everything after the rows is the
+    same code.
+    detector='padim' = one Gaussian per map position (PositionGaussianDetector: PaDiM; the Mahalanobis distance to the position's
+    Gaussian over `channels` randomly chosen columns); needs patch_localization=True, localization='dense' and bank='train'; takes
+    image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed', 'factor'} of that detector
+    ('padim' only).
+    `metric`: 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's Euclidean distance between the raw rows
+    (AnomalyDetector(metric='euclidean'): search, coreset selection and image scores all in that metric); 'knn' only."""
+    cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
+                                 neighbours, detector_options)
+    del TIMELINE[:]
+    print('>>> initializing inference')
+    plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
+    print('>>> preparing model')
+    _mark("prefetch-started")
+    model, tester = _load_model(model_input_dir, patch_localization, localization, plan.prefetch)
+    print('>>> preparing datamodule')
+    if mvtec_inference:
+        model.enable_mvtec_inference()
+    datamodule = plan.datamodule if mvtec_inference else PretextTaskDatamodule(subject=subject, root_dir=dataset_dir, min_dataset_length=500, batch_size=1)
+    print('>>> doing prediction')
+    output, emb_dev, n_pred = _predict(model, tester, datamodule, plan)
+    print('>>> anomaly detection phase')
+    if patch_localization:
+        det_kw.update(patch_level=True, batch=n_pred, num_patches=model.num_patches)
+    detector = cls(**det_kw)
+    normality, groups = _normality_rows(model, tester, output, plan, dataset_dir, subject, mvtec_inference)
+    output.to_cpu()
+    _fit_or_receive(detector, normality, groups, plan)
+    _mark("bank-fitted")
+    return _score_and_gather(detector, output, emb_dev, n_pred, image_scores, neighbours, plan.world, datamodule)
 
 
 def _split_container(output: ModelOutputsContainer, n_images: int):
@@ -763,13 +766,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
     `neighbours`, `localization`, `detector_options` and `metric` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns."""
-    _check_detector(detector)
-    _check_metric(metric, detector)
-    _check_bank(bank)
-    _check_coreset(coreset, detector)
-    _check_image_scores(image_scores, neighbours, patch_localization, detector)
-    _check_localization(localization, patch_localization)
-    _check_padim(detector, patch_localization, localization, bank, detector_options)
+    _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}

@@ -171,6 +171,27 @@ def test_detector_matches_sklearn_end_to_end():
     assert torch.equal(det2.predict(q), det.predict(q))
 
 
+@pytest.mark.parametrize("name,kw", [("knn", {"metric": "cosine"}), ("knn", {"metric": "euclidean"}), ("gde", {}),
+                                     ("padim", {"factor": "host"}), ("padim", {"factor": "device"})])
+def test_load_state_scores_like_the_fitted_detector(name, kw):
+    """Every detector of models.DETECTORS, at its smallest legal shapes: state() loaded into a fresh instance constructed with the
+    same arguments gives the bits of the fitted one (what a rank that receives the broadcast scores with)."""
+    from self_supervised.models import DETECTORS
+    if name == "padim":
+        kw = {"patch_level": True, "batch": 6, "num_patches": 4, "channels": 32, **kw}        # 6 images x 4 positions x 32 columns
+    elif name == "knn":
+        kw = {"patch_level": True, "batch": 12, "num_patches": 4, **kw}                        # 48 rows x 32 columns
+    bank, q = _rows(48 if name != "padim" else 24, 32, seed=31), _rows(48 if name != "padim" else 24, 32, seed=32, spread=1.5)
+    fitted, fresh = DETECTORS[name](**kw), DETECTORS[name](**kw)
+    fitted.fit(bank, split=False)
+    fresh.load_state(fitted.state())
+    want = fitted.predict(q)
+    assert torch.isfinite(want).all() and want.min() > 0
+    assert torch.equal(fresh.predict(q), want)
+    if name != "gde":                   # (a Gaussian over all rows has no image score)
+        assert torch.equal(fresh.image_scores(q, 'max'), fitted.image_scores(q, 'max', scores=want.reshape(-1)))
+
+
 def _seeded_tree(tmp_path, seeded_sd):
     from self_supervised import datasets
     datasets._DataModule.num_workers = 0

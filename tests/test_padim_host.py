@@ -151,7 +151,7 @@ def test_tools_refuse_from_the_arguments_alone(tmp_path, kw, match):
 
 def test_padim_is_a_known_detector_and_image_scores_max_is_allowed(tmp_path):
     from self_supervised import tools
-    assert tools.DETECTORS == ('knn', 'gde', 'padim')
+    assert tuple(tools.DETECTORS) == ('knn', 'gde', 'padim')
     assert tools._check_image_scores('max', 9, True, 'padim') == 'max'
     assert tools._check_padim('padim', True, 'dense', 'train', {"channels": 32, "seed": 4}) == {"channels": 32, "seed": 4}
     assert tools._check_padim('knn', False, 'patches', 'reference', None) == {}
