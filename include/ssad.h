@@ -684,6 +684,38 @@ int64_t ssad_obj_mask_workspace(int B, int H, int W);
 int ssad_obj_mask(const uint8_t* rgb, uint8_t* mask, uint8_t* edges, int B, int H, int W, const double* gauss_w_host, int radius,
                   double low, double high, void* workspace, void* stream);
 
+/* Defect regions (csrc/regions.hip): what a user does with an anomaly map after the threshold.  All outputs are integers (and
+ * min / max of the scores): exact, and the same bits on every call.
+ * ssad_label_regions: connected components of a batch of binary images [n][H][W].  Foreground is EITHER scores fp32 with
+ *   scores >= threshold (the rule of ssad_confusion_counts: NaN is background, +inf >= +inf is foreground) OR mask uint8 != 0;
+ *   exactly one of the two pointers is non-NULL.  connectivity: 8 or 4.  labels int32 [n][H][W]: 0 = background, components
+ *   numbered 1 .. counts[i] per image in raster order of their first pixel -- scipy.ndimage.label's array exactly; counts int32
+ *   [n]; offsets int32 [n + 1] = exclusive prefix sum of counts.  n, H, W >= 1, H * W < 2^30, n * H * W < 2^31.  workspace:
+ *   ssad_label_regions_workspace(n, H, W) bytes.  A union-find over pixel indices in tiles of ssad_label_regions_tile() pixels a
+ *   side (LDS), merged across tile borders by atomic minima: the work does not grow with the length of a component's path.
+ * ssad_region_stats: with R = offsets[n] (read back by the caller; R = 0 writes nothing), per region in (image, label) order:
+ *   area int32 [R]; bbox int32 [R][4] = x0, y0, x1, y1 with inclusive maxima; coord_sum int64 [R][2] = sum of x, sum of y (the
+ *   centroid as an exact rational); and, when scores is given (else all three NULL), peak fp32 [R] = the largest score of the
+ *   region and peak_pos int32 [R] = the smallest raster index within the image that attains it (NaN orders below every number).
+ * ssad_region_filter: mask_out uint8 [n][H][W] = 1 where the pixel's region r has keep[r] != 0 (keep uint8 [R]).  With labels_out
+ *   (may be labels itself), counts_out [n] and offsets_out [n + 1] (all three or none): the kept regions renumbered 1 .. per
+ *   image in the same order; then workspace holds ssad_region_filter_workspace(R) bytes.
+ * ssad_pro_weights: the two planes of ssad_pro_curve from labelled ground truths: fp_w uint8 = (label == 0), pro_w fp64 = 1.0 /
+ *   area of the pixel's region (the correctly rounded quotient), 0 on background.
+ * A bad argument returns 2 before any launch. */
+int ssad_label_regions_tile(void);
+int64_t ssad_label_regions_workspace(int64_t n, int H, int W);
+int ssad_label_regions(const float* scores, float threshold, const uint8_t* mask, int64_t n, int H, int W, int connectivity,
+                       int32_t* labels, int32_t* counts, int32_t* offsets, void* workspace, int64_t workspace_bytes, void* stream);
+int ssad_region_stats(const float* scores, const int32_t* labels, const int32_t* offsets, int64_t n, int H, int W, int64_t R,
+                      int32_t* area, int32_t* bbox, int64_t* coord_sum, float* peak, int32_t* peak_pos, void* stream);
+int64_t ssad_region_filter_workspace(int64_t R);
+int ssad_region_filter(const int32_t* labels, const int32_t* offsets, const uint8_t* keep, int64_t n, int H, int W, int64_t R,
+                       uint8_t* mask_out, int32_t* labels_out, int32_t* counts_out, int32_t* offsets_out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int ssad_pro_weights(const int32_t* labels, const int32_t* offsets, const int32_t* area, int64_t n, int H, int W, uint8_t* fp_w,
+                     double* pro_w, void* stream);
+
 /* ---- half-tensor forms of the precision-16 training step ----
  * pl.Trainer(precision=16) (src/self_supervised/tools.py:263, :296) runs the reference's training_step (models.py:256-277) under
  * torch.autocast(float16): every conv / linear / BatchNorm output of the trunk is an fp16 tensor in memory and so is its gradient.

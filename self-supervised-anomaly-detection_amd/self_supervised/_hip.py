@@ -172,6 +172,14 @@ SIGNATURES = {
     "ssad_resize_bicubic_u8": [_c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_fp],
     "ssad_u8hwc_to_f32chw_norm": [_c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                   _c_fp],
+    # defect regions (csrc/regions.hip)
+    "ssad_label_regions_tile": [],
+    "ssad_label_regions_workspace": [_c_l, _c_i, _c_i],
+    "ssad_label_regions": [_c_fp, _c_f, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_fp],
+    "ssad_region_stats": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_l, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
+    "ssad_region_filter_workspace": [_c_l],
+    "ssad_region_filter": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_l, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_fp],
+    "ssad_pro_weights": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp],
     # half-tensor forms of the precision-16 training step (include/ssad.h, last section)
     "ssad_cvt_f32_f16": [_c_fp, _c_fp, _c_l, _c_fp],
     "ssad_flip_transpose_batch_h": [_c_fp, _c_fp, ctypes.POINTER(ctypes.c_int64), _c_i, _c_fp],
@@ -225,7 +233,7 @@ SIGNATURES = {
     "ssad_stem_wgrad_h": [_c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp],
 }
 RESTYPES = {"ssad_conv3x3_c64_stats_rows": _c_l, "ssad_conv3x3_h_stats_rows": _c_l, "ssad_conv3x3_hw_stats_rows": _c_l, "ssad_conv3x3_hw_packed_size": _c_l, "ssad_colreduce_workspace": _c_l, "ssad_conv_stats_workspace": _c_l, "ssad_stem_wgrad_workspace": _c_l, "ssad_auroc_workspace": _c_l, "ssad_obj_mask_workspace": _c_l, "ssad_pro_curve_workspace": _c_l,
-            "ssad_best_f1_workspace": _c_l}
+            "ssad_best_f1_workspace": _c_l, "ssad_label_regions_workspace": _c_l, "ssad_region_filter_workspace": _c_l}
 
 _lib = None
 

@@ -59,6 +59,27 @@ class ModelOutputsContainer:
         return parts
 
 
+class RegionsOutput:
+    """What ``tools.defect_regions`` hands back: ``pred_masks`` uint8 [n][1][H][W] and ``labels`` int32 [n][1][H][W] on the device
+    (regions below ``min_area`` removed, the rest numbered 1 .. per image), and ``regions``: per image a list of dicts of host
+    values -- ``box`` (x0, y0, x1, y1, maxima inclusive), ``area``, ``centroid`` (x, y), ``score`` (the region's peak, anomalib's
+    ``box_scores``) and ``peak`` (x, y)."""
+
+    def __init__(self, pred_masks=None, labels=None, regions=None, threshold=None) -> None:
+        self.pred_masks = pred_masks
+        self.labels = labels
+        self.regions = regions if regions is not None else []
+        self.threshold = threshold
+
+    @property
+    def pred_boxes(self) -> list:
+        return [[r['box'] for r in img] for img in self.regions]
+
+    @property
+    def box_scores(self) -> list:
+        return [[r['score'] for r in img] for img in self.regions]
+
+
 class EvaluationOutputContainer:
     def __init__(self) -> None:
         self.auroc = None

@@ -202,14 +202,36 @@ def compute_iou_gpu(scores, targets, threshold) -> float:
     return float(np.mean(ious))
 
 
-def compute_pro_gpu(anomaly_maps, ground_truth_maps):
+def _pro_weights_device(maps, ground_truth_maps):
+    """The two weight planes and the two counts of compute_pro_gpu without the host loop: the ground truths go up as uint8 and are
+    labelled (8-connected), measured and weighted there (csrc/regions.hip); bit-equal to the numpy planes."""
+    from . import ops
+    gts = torch.as_tensor(ground_truth_maps)
+    gts = (gts.reshape((-1,) + tuple(gts.shape[-2:])) != 0).to(torch.uint8).to(maps.device)
+    assert maps.numel() == gts.numel(), "maps and ground truths differ in size"
+    labels, _, offsets = ops.label_regions(gts, connectivity=8)
+    n_regions = int(offsets[-1].item())
+    area, _, _, _, _ = ops.region_stats(labels, offsets, num_regions=n_regions)
+    fpd, prd = ops.pro_weights(labels, offsets, area)
+    n_ok = gts.numel() - int(area.sum().item())
+    return fpd, prd, float(n_ok), n_regions
+
+
+def compute_pro_gpu(anomaly_maps, ground_truth_maps, labelling='host'):
     """compute_pro for device-resident maps [n][H][W]: the ground-truth regions are labelled on the host (a few dozen small masks),
     the 6 M scores are sorted, weighted, accumulated and compacted on the device (ssad_pro_curve).  Returns (fprs, pros) as numpy
-    arrays from (0, 0) to (1, 1); equal to compute_pro up to the summation order of the fp64 running sum (~1e-13)."""
+    arrays from (0, 0) to (1, 1); equal to compute_pro up to the summation order of the fp64 running sum (~1e-13).
+    labelling='device' (opt-in) labels the ground truths on the device as well (ops.label_regions -> region_stats -> pro_weights):
+    the same planes bit for bit, hence the same arrays."""
     from . import _hip
+    if labelling not in ('host', 'device'):
+        raise ValueError(f"compute_pro_gpu: labelling is 'host' or 'device', got {labelling!r}")
     maps = anomaly_maps.detach().float().contiguous()
     if not maps.is_cuda:
         raise RuntimeError("compute_pro_gpu needs GPU maps; use compute_pro on the host")
+    if labelling == 'device':
+        fpd, prd, n_ok, n_regions = _pro_weights_device(maps, ground_truth_maps)
+        return _pro_curve_device(maps, fpd, prd, n_ok, n_regions)
     gts = _np(ground_truth_maps)
     gts = gts.reshape((-1,) + gts.shape[-2:])
     fp_w = np.zeros(gts.shape, dtype=np.uint8)
@@ -228,6 +250,22 @@ def compute_pro_gpu(anomaly_maps, ground_truth_maps):
     n_ok = float(fp_w.sum())
     dev = maps.device
     fpd, prd = torch.from_numpy(fp_w.reshape(-1)).to(dev), torch.from_numpy(pro_w.reshape(-1)).to(dev)
+    nbytes = _hip.lib().ssad_pro_curve_workspace(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    fprs = torch.empty(n, dtype=torch.float32, device=dev)
+    pros = torch.empty(n, dtype=torch.float64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    _hip.check(_hip.lib().ssad_pro_curve(maps.data_ptr(), fpd.data_ptr(), prd.data_ptr(), n, max(n_ok, 1.0), float(max(n_regions, 1)),
+                                         ws.data_ptr(), nbytes, fprs.data_ptr(), pros.data_ptr(), count.data_ptr(), _hip.stream()))
+    k = int(count.item())
+    f, p = fprs[:k].cpu().numpy(), pros[:k].cpu().numpy()
+    return np.concatenate(([0.0], f, [1.0])), np.concatenate(([0.0], p, [1.0]))
+
+
+def _pro_curve_device(maps, fpd, prd, n_ok, n_regions):
+    """ssad_pro_curve on planes that are already on the device (compute_pro_gpu(labelling='device'))."""
+    from . import _hip
+    n, dev = maps.numel(), maps.device
     nbytes = _hip.lib().ssad_pro_curve_workspace(n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     fprs = torch.empty(n, dtype=torch.float32, device=dev)

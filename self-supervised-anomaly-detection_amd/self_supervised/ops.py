@@ -1149,6 +1149,132 @@ def obj_mask_batch(rgb, sigma=1.5, low=5, high=15, chunk=64, return_edges=False)
     return (mask.bool(), edges.bool()) if return_edges else mask.bool()
 
 
+# ---- defect regions (csrc/regions.hip): integers only, bit-equal to scipy.ndimage on the host ----
+REGION_TILE = 32      # tile side of the labelling kernel (ssad_label_regions_tile()): sizes around its multiples are the ragged cases
+
+
+def _regions_dev(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError(f"{name} needs GPU tensors (csrc/regions.hip; scipy.ndimage.label is the host statement)")
+    return t
+
+
+def _regions_3d(x, name):
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    if x.dim() != 3 or 0 in x.shape:
+        raise ValueError(f"{name}: expected [n][H][W] or [n][1][H][W] with n, H, W >= 1, got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def label_regions(x, threshold=None, connectivity=8):
+    """Connected components of a batch of binary images on the device.  x [n][H][W] or [n][1][H][W]: a float tensor with a
+    `threshold` (foreground = x >= threshold; NaN is background) or a bool / uint8 mask (foreground = nonzero).  Returns
+    (labels int32 [n][H][W], counts int32 [n], offsets int32 [n + 1]); labels equals scipy.ndimage.label's array (8: 3 x 3 ones,
+    4: the cross), components numbered 1 .. counts[i] per image."""
+    _regions_dev(x, "label_regions")
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_regions: connectivity is 4 or 8, got {connectivity!r}")
+    x = _regions_3d(x, "label_regions")
+    scores = mask = None
+    if x.is_floating_point():
+        if threshold is None:
+            raise ValueError("label_regions: a float tensor needs a threshold")
+        scores, thr = x.float().contiguous(), float(threshold)
+    elif x.dtype in (torch.bool, torch.uint8):
+        if threshold is not None:
+            raise ValueError("label_regions: a mask takes no threshold")
+        mask, thr = x.to(torch.uint8).contiguous(), 0.0
+    else:
+        raise ValueError(f"label_regions: float scores or a bool / uint8 mask, got {x.dtype}")
+    n, h, w = x.shape
+    lib = _hip.lib()
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=x.device)
+    counts = torch.empty(n, dtype=torch.int32, device=x.device)
+    offsets = torch.empty(n + 1, dtype=torch.int32, device=x.device)
+    nbytes = lib.ssad_label_regions_workspace(n, h, w)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _run("label_regions", 0.0, 5.0 * n * h * w,
+         lambda: lib.ssad_label_regions(None if scores is None else scores.data_ptr(), thr, None if mask is None else mask.data_ptr(),
+                                        n, h, w, connectivity, labels.data_ptr(), counts.data_ptr(), offsets.data_ptr(), ws.data_ptr(),
+                                        nbytes, _hip.stream()))
+    return labels, counts, offsets
+
+
+def _regions_args(labels, offsets, name):
+    _regions_dev(labels, name)
+    _regions_dev(offsets, name)
+    labels = _regions_3d(labels, name)
+    n, h, w = labels.shape
+    if labels.dtype != torch.int32 or offsets.dtype != torch.int32 or offsets.numel() != n + 1 or not offsets.is_contiguous():
+        raise ValueError(f"{name}: labels int32 [n][H][W] and offsets int32 [n + 1] as label_regions returns them")
+    return labels, n, h, w
+
+
+def region_stats(labels, offsets, scores=None, num_regions=None):
+    """Per region, in (image, label) order, as device tensors: area int32 [R], bbox int32 [R][4] (x0, y0, x1, y1, maxima
+    inclusive), coord_sum int64 [R][2] (sum of x, sum of y) and, with `scores` [n][H][W], peak fp32 [R] and peak_pos int32 [R]
+    (the smallest raster index within the image that attains the peak); without scores the last two are None.  R = offsets[n]
+    is read back once unless `num_regions` passes it."""
+    labels, n, h, w = _regions_args(labels, offsets, "region_stats")
+    r = int(offsets[n].item()) if num_regions is None else int(num_regions)
+    dev = labels.device
+    area = torch.empty(r, dtype=torch.int32, device=dev)
+    bbox = torch.empty((r, 4), dtype=torch.int32, device=dev)
+    csum = torch.empty((r, 2), dtype=torch.int64, device=dev)
+    peak = pos = None
+    if scores is not None:
+        scores = _regions_3d(_regions_dev(scores, "region_stats"), "region_stats").float().contiguous()
+        if scores.shape != labels.shape:
+            raise ValueError("region_stats: scores and labels differ in shape")
+        peak = torch.empty(r, dtype=torch.float32, device=dev)
+        pos = torch.empty(r, dtype=torch.int32, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    _run("region_stats", 0.0, 8.0 * labels.numel(),
+         lambda: _hip.lib().ssad_region_stats(p(scores), labels.data_ptr(), offsets.data_ptr(), n, h, w, r, area.data_ptr(),
+                                              bbox.data_ptr(), csum.data_ptr(), p(peak), p(pos), _hip.stream()))
+    return area, bbox, csum, peak, pos
+
+
+def region_filter(labels, offsets, keep, renumber=True):
+    """Keeps the regions r with keep[r] != 0 (keep: bool / uint8 [R] on the device).  Returns mask uint8 [n][H][W] and, when
+    `renumber`, (mask, labels_out, counts_out, offsets_out) with the kept regions numbered 1 .. per image in the same order."""
+    labels, n, h, w = _regions_args(labels, offsets, "region_filter")
+    keep = _regions_dev(keep, "region_filter").reshape(-1).to(torch.uint8).contiguous()
+    r = keep.numel()
+    dev = labels.device
+    lib = _hip.lib()
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    lab2 = cnt2 = off2 = ws = None
+    nbytes = 0
+    if renumber:
+        lab2 = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+        cnt2 = torch.empty(n, dtype=torch.int32, device=dev)
+        off2 = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        nbytes = lib.ssad_region_filter_workspace(r)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    _run("region_filter", 0.0, 9.0 * labels.numel(),
+         lambda: lib.ssad_region_filter(labels.data_ptr(), offsets.data_ptr(), p(keep) if r else None, n, h, w, r, mask.data_ptr(),
+                                        p(lab2), p(cnt2), p(off2), p(ws), nbytes, _hip.stream()))
+    return (mask, lab2, cnt2, off2) if renumber else mask
+
+
+def pro_weights(labels, offsets, area):
+    """The two weight planes of the PRO curve from labelled ground truths: fp_w uint8 [n * H * W] = (label == 0) and pro_w fp64 =
+    1.0 / area of the pixel's region, 0 on background -- bit-equal to what metrics.compute_pro_gpu builds in numpy."""
+    labels, n, h, w = _regions_args(labels, offsets, "pro_weights")
+    area = _regions_dev(area, "pro_weights")
+    if area.dtype != torch.int32 or not area.is_contiguous():
+        raise ValueError("pro_weights: area int32 [R] as region_stats returns it")
+    fp_w = torch.empty(labels.numel(), dtype=torch.uint8, device=labels.device)
+    pro_w = torch.empty(labels.numel(), dtype=torch.float64, device=labels.device)
+    _run("pro_weights", 0.0, 13.0 * labels.numel(),
+         lambda: _hip.lib().ssad_pro_weights(labels.data_ptr(), offsets.data_ptr(), area.data_ptr(), n, h, w, fp_w.data_ptr(),
+                                             pro_w.data_ptr(), _hip.stream()))
+    return fp_w, pro_w
+
+
 def gradcam_map(act, alpha):
     """act NHWC [B][U][V][C], alpha [B][C] (may be a column slice of a wider matrix) -> [B][1][U][V] weighted sums."""
     b, u, v, c = act.shape

@@ -16,7 +16,7 @@ from torch import Tensor
 
 from . import metrics as mtr
 from . import ops
-from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
+from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer, RegionsOutput
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
 from . import models
 from .models import PeraNet, PositionGaussianDetector, check_coreset, check_image_scores, check_metric
@@ -26,7 +26,10 @@ from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast
 class Evaluator:
     """tools.py:52-146: scores an inference output; pixel level when ``patch_level`` (maps vs ground truths)."""
 
-    def __init__(self, evaluation_metrics: list = []) -> None:
+    def __init__(self, evaluation_metrics: list = [], pro_labelling: str = 'host') -> None:
+        if pro_labelling not in ('host', 'device'):
+            raise ValueError(f"pro_labelling is 'host' or 'device', got {pro_labelling!r}")
+        self.pro_labelling = pro_labelling            # where compute_pro_gpu labels the ground truths (device maps only)
         self.evaluation_metrics = np.array(evaluation_metrics)
         self.scores = EvaluationOutputContainer()
         self.curves = {}
@@ -57,7 +60,9 @@ class Evaluator:
             if 'f1-score' in self.evaluation_metrics:
                 self.scores.f1_score = mtr.compute_f1_gpu(targets_dev, scores, threshold)
             if 'aupro' in self.evaluation_metrics:
-                fprs, pros = mtr.compute_pro_gpu(output_container.anomaly_maps.squeeze(1), output_container.ground_truths.squeeze(1))
+                extra = {} if self.pro_labelling == 'host' else {'labelling': self.pro_labelling}
+                fprs, pros = mtr.compute_pro_gpu(output_container.anomaly_maps.squeeze(1), output_container.ground_truths.squeeze(1),
+                                                 **extra)
                 self.scores.aupro = mtr.compute_aupro(fprs, pros, 0.3)
                 self.curves['pro'] = (fprs, pros)
             if 'iou' in self.evaluation_metrics:
@@ -722,6 +727,46 @@ def upsample(anomaly_maps: Tensor, target_size: int = 256, verbose: bool = True)
             raise RuntimeError("tools.upsample runs on the MI355X HIP kernel only (no CPU fallback)")
         m = m.cuda()
     return ops.blur_relu_bilinear(m.contiguous(), 7, target_size)
+
+
+def defect_regions(anomaly_maps: Tensor, threshold: float, min_area: int = 1, connectivity: int = 8) -> RegionsOutput:
+    """Where the defects are: thresholds the device maps ``tools.upsample`` returns (``maps >= threshold``; pass
+    ``output.threshold`` or your own), splits the mask into connected regions, drops those smaller than ``min_area`` pixels and
+    describes the rest (csrc/regions.hip; anomalib's pred_masks / pred_boxes / box_scores).  Masks and labels stay on the device;
+    the regions' numbers come back in one copy.  Equal to scipy.ndimage.label + numpy on the host, exactly."""
+    if connectivity not in (4, 8):
+        raise ValueError(f"defect_regions: connectivity is 4 or 8, got {connectivity!r}")
+    if not isinstance(min_area, (int, np.integer)) or isinstance(min_area, bool) or min_area < 1:
+        raise ValueError(f"defect_regions: min_area is an integer >= 1, got {min_area!r}")
+    if threshold is None or np.isnan(float(threshold)):
+        raise ValueError("defect_regions: a threshold is required and cannot be NaN (pass output.threshold or your own)")
+    maps = torch.as_tensor(anomaly_maps)
+    if not ((maps.dim() == 3 or (maps.dim() == 4 and maps.shape[1] == 1)) and maps.numel() > 0 and maps.is_floating_point()):
+        raise ValueError(f"defect_regions: float maps [n][1][H][W] or [n][H][W], got {tuple(maps.shape)} {maps.dtype}")
+    if not maps.is_cuda:
+        raise RuntimeError("tools.defect_regions runs on the MI355X HIP kernels only (no CPU fallback): pass the device maps of "
+                           "tools.upsample")
+    scores = (maps[:, 0] if maps.dim() == 4 else maps).detach().float().contiguous()
+    n, h, w = scores.shape
+    labels, _, offsets = ops.label_regions(scores, float(threshold), connectivity)
+    r0 = int(offsets[n].item())
+    area0 = ops.region_stats(labels, offsets, num_regions=r0)[0]
+    mask, labels, counts, offsets = ops.region_filter(labels, offsets, area0 >= int(min_area))
+    cnt = counts.cpu().tolist()
+    r = sum(cnt)
+    area, bbox, csum, peak, pos = ops.region_stats(labels, offsets, scores, num_regions=r)
+    # one copy for all regions: nine int64 columns, the peak as its bit pattern
+    table = torch.cat([area.long().unsqueeze(1), bbox.long(), csum, peak.view(torch.int32).long().unsqueeze(1),
+                       pos.long().unsqueeze(1)], dim=1).cpu().numpy() if r else np.zeros((0, 9), dtype=np.int64)
+    regions, k = [], 0
+    for c in cnt:
+        rows = []
+        for a, x0, y0, x1, y1, sx, sy, pk, pp in table[k:k + c].tolist():
+            rows.append({'box': (x0, y0, x1, y1), 'area': a, 'centroid': (sx / a, sy / a),
+                         'score': float(np.array(pk, dtype=np.int64).astype(np.int32).view(np.float32)), 'peak': (pp % w, pp // w)})
+        regions.append(rows)
+        k += c
+    return RegionsOutput(mask.unsqueeze(1), labels.unsqueeze(1), regions, float(threshold))
 
 
 def image_auroc(output: ModelOutputsContainer) -> float:
