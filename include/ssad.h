@@ -716,6 +716,21 @@ int ssad_region_filter(const int32_t* labels, const int32_t* offsets, const uint
 int ssad_pro_weights(const int32_t* labels, const int32_t* offsets, const int32_t* area, int64_t n, int H, int W, uint8_t* fp_w,
                      double* pro_w, void* stream);
 
+/* Anomaly maps as PatchCore and PaDiM define them (csrc/resize_gaussian.hip): bilinear resize (align_corners=False) of maps
+ * [n][h][w] to T x T, THEN a Gaussian of sigma image pixels, as the one linear operator out = A_y M A_x^T, A = G R per axis.  R is
+ * the [T][extent] bilinear matrix (src = max((dst + 0.5) extent / T - 0.5, 0), neighbour clamped); G the [T][T] Gaussian of radius
+ * r = int(4 sigma + 0.5), taps exp(-0.5 (d / sigma)^2) normalised in float64, indices outside [0, T) folded back: border
+ * 'symmetric' folds b a | a b (scipy.ndimage mode='reflect', what the PatchCore and PaDiM code runs), border 'reflect' folds
+ * c b | a b c (torch / kornia reflect padding, what anomalib runs).  The caller builds A in float64 and passes each axis in band
+ * form: first int32 [T] = the first source index of the row's run of non-zeros, weights fp32 [T][K] = A[d][first[d] .. + K)
+ * rounded once, zero-padded, first[d] + K <= extent; K_y <= h, K_x <= w.  out [n][T][T] fp32: per pixel two chains of K FMAs in
+ * ascending tap order -- the same bits whatever n and band.  band: output rows per workgroup, 0 = ssad_resize_gaussian_band(h, w,
+ * T, Ky) (the largest of 32, 16, .. whose source rows and intermediate fit the LDS of a launch; 0 when none does).  A bad argument
+ * (null pointer, a size or K below 1, a band that does not fit) returns 2 before any launch. */
+int ssad_resize_gaussian_band(int h, int w, int T, int Ky);
+int ssad_resize_gaussian(const float* maps, int64_t n, int h, int w, const int32_t* y_first, const float* y_weights, int Ky,
+                         const int32_t* x_first, const float* x_weights, int Kx, int T, int band, float* out, void* stream);
+
 /* ---- half-tensor forms of the precision-16 training step ----
  * pl.Trainer(precision=16) (src/self_supervised/tools.py:263, :296) runs the reference's training_step (models.py:256-277) under
  * torch.autocast(float16): every conv / linear / BatchNorm output of the trunk is an fp16 tensor in memory and so is its gradient.

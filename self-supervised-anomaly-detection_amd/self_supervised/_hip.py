@@ -180,6 +180,9 @@ SIGNATURES = {
     "ssad_region_filter_workspace": [_c_l],
     "ssad_region_filter": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_l, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_fp],
     "ssad_pro_weights": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp],
+    # resize, then Gaussian (csrc/resize_gaussian.hip)
+    "ssad_resize_gaussian_band": [_c_i, _c_i, _c_i, _c_i],
+    "ssad_resize_gaussian": [_c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_fp, _c_fp],
     # half-tensor forms of the precision-16 training step (include/ssad.h, last section)
     "ssad_cvt_f32_f16": [_c_fp, _c_fp, _c_l, _c_fp],
     "ssad_flip_transpose_batch_h": [_c_fp, _c_fp, ctypes.POINTER(ctypes.c_int64), _c_i, _c_fp],

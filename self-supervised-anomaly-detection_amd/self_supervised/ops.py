@@ -1086,6 +1086,92 @@ def blur_relu_bilinear(maps, ksize=7, target=256):
     return out
 
 
+# ---- resize, then Gaussian (csrc/resize_gaussian.hip): the anomaly map of PatchCore and PaDiM as one banded operator per axis ----
+RESIZE_GAUSSIAN_BORDERS = ('symmetric', 'reflect')
+_RESIZE_GAUSSIAN_TABLES = {}
+
+
+def _resize_gaussian_matrix(extent, T, sigma, border):
+    """A = G R in float64, [T][extent]: R the bilinear matrix of F.interpolate(align_corners=False), G the Gaussian of
+    scipy.ndimage.gaussian_filter (radius int(4 sigma + 0.5)) with its border folded back into [0, T)."""
+    import numpy as np
+    d = np.arange(T)
+    src = np.maximum((d + 0.5) * extent / T - 0.5, 0.0)
+    i0 = np.minimum(np.floor(src).astype(np.int64), extent - 1)
+    i1 = np.minimum(i0 + 1, extent - 1)
+    lam = src - i0
+    R = np.zeros((T, extent))
+    np.add.at(R, (d, i0), 1.0 - lam)
+    np.add.at(R, (d, i1), lam)
+    r = int(4.0 * sigma + 0.5)
+    k = np.arange(-r, r + 1)
+    taps = np.exp(-0.5 * (k / sigma) ** 2)
+    taps /= taps.sum()
+    j = d[:, None] + k[None, :]
+    if border == 'symmetric':                                   # b a | a b: scipy.ndimage mode='reflect'
+        j = np.where(j < 0, -j - 1, np.where(j >= T, 2 * T - 1 - j, j))
+    else:                                                       # c b | a b c: torch / kornia reflect padding
+        j = np.where(j < 0, -j, np.where(j >= T, 2 * T - 2 - j, j))
+    G = np.zeros((T, T))
+    np.add.at(G, (np.repeat(d, k.size), j.reshape(-1)), np.tile(taps, T))
+    return G @ R
+
+
+def resize_gaussian_operator(h, T, sigma=4.0, border='symmetric', device=None):
+    """Band form of A = G R for one axis of `h` source cells and `T` output pixels: (first int32 [T], weights fp32 [T][K], K) --
+    row d of A is weights[d] at source indices first[d] .. first[d] + K - 1, built in float64, rounded once, zero-padded.  Cached
+    per (h, T, sigma, border, device); device None keeps the tables on the host."""
+    import numpy as np
+    h, T, sigma = int(h), int(T), float(sigma)
+    if not sigma > 0.0:
+        raise ValueError(f"resize_gaussian: sigma must be positive, got {sigma!r}")
+    if border not in RESIZE_GAUSSIAN_BORDERS:
+        raise ValueError(f"resize_gaussian: border is 'symmetric' (scipy.ndimage) or 'reflect' (torch / kornia), got {border!r}")
+    if h < 1 or T < 1:
+        raise ValueError(f"resize_gaussian: sizes must be positive, got {h} -> {T}")
+    if int(4.0 * sigma + 0.5) >= T:
+        raise ValueError(f"resize_gaussian: the radius int(4 sigma + 0.5) = {int(4.0 * sigma + 0.5)} must be below the target size {T}")
+    key = (h, T, sigma, border, None if device is None else str(torch.device(device)))
+    t = _RESIZE_GAUSSIAN_TABLES.get(key)
+    if t is None:
+        A = _resize_gaussian_matrix(h, T, sigma, border)
+        nz = A != 0.0
+        lo = nz.argmax(axis=1)
+        hi = h - 1 - nz[:, ::-1].argmax(axis=1)
+        K = int((hi - lo + 1).max())
+        first = np.minimum(lo, h - K)
+        weights = A[np.arange(T)[:, None], first[:, None] + np.arange(K)[None, :]].astype(np.float32)
+        first_t, weights_t = torch.from_numpy(first.astype(np.int32)), torch.from_numpy(weights)
+        if device is not None:
+            first_t, weights_t = first_t.to(device), weights_t.to(device)
+        t = _RESIZE_GAUSSIAN_TABLES[key] = (first_t, weights_t, K)
+    return t
+
+
+def resize_gaussian(maps, target, sigma=4.0, border='symmetric'):
+    """maps [n][1][h][w] or [n][h][w] (float, on the device) -> [n][1][target][target] fp32: bilinear resize (align_corners=False),
+    then the Gaussian of `sigma` output pixels -- scipy.ndimage.gaussian_filter with border='symmetric' (the PatchCore / PaDiM
+    code), torch reflect padding with border='reflect' (anomalib) -- as out = A_y M A_x^T in one launch."""
+    target = int(target)
+    if not (torch.is_tensor(maps) and maps.is_floating_point() and (maps.dim() == 3 or (maps.dim() == 4 and maps.shape[1] == 1))
+            and maps.numel() > 0):
+        raise ValueError(f"resize_gaussian: float maps [n][1][h][w] or [n][h][w], got "
+                         f"{tuple(maps.shape) if torch.is_tensor(maps) else type(maps)}")
+    n, h, w = maps.shape[0], maps.shape[-2], maps.shape[-1]
+    resize_gaussian_operator(h, target, sigma, border)          # the ValueErrors, before anything touches the device
+    if not maps.is_cuda:
+        raise RuntimeError("resize_gaussian needs GPU tensors (csrc/resize_gaussian.hip; there is no CPU fallback)")
+    m = maps.detach().reshape(n, h, w).float().contiguous()
+    yf, yw, ky = resize_gaussian_operator(h, target, sigma, border, m.device)
+    xf, xw, kx = (yf, yw, ky) if w == h else resize_gaussian_operator(w, target, sigma, border, m.device)
+    out = _new((n, 1, target, target), m)
+    _run("resize_gaussian", 0.0, 4.0 * (m.numel() + out.numel()),
+         lambda: _hip.lib().ssad_resize_gaussian(_hip.ptr(m), n, h, w, _hip.ptr(yf, dtype=torch.int32), _hip.ptr(yw), ky,
+                                                 _hip.ptr(xf, dtype=torch.int32), _hip.ptr(xw), kx, target, 0, _hip.ptr(out),
+                                                 _hip.stream()))
+    return out
+
+
 _RESAMPLE_TABLES = {}
 
 

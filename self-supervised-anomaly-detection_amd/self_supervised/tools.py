@@ -717,8 +717,14 @@ def _split_container(output: ModelOutputsContainer, n_images: int):
     return output.split(n_images)
 
 
-def upsample(anomaly_maps: Tensor, target_size: int = 256, verbose: bool = True):
-    """tools.py:394-399: relu(gaussian_blur(k=7)) then bilinear to target_size, one fused kernel."""
+def upsample(anomaly_maps: Tensor, target_size: int = 256, verbose: bool = True, method: str = 'reference', sigma: float = 4.0,
+             border: str = 'symmetric'):
+    """method='reference' (tools.py:394-399): relu(gaussian_blur(k=7)) then bilinear to target_size, one fused kernel.
+    method='resize_blur' (opt-in): the map PatchCore and PaDiM define -- bilinear to target_size, THEN a Gaussian of `sigma` image
+    pixels; border='symmetric' is scipy.ndimage.gaussian_filter's (their official code), 'reflect' torch's padding (anomalib);
+    one kernel as well (ops.resize_gaussian).  `sigma` and `border` belong to 'resize_blur' alone."""
+    if method not in ('reference', 'resize_blur'):
+        raise ValueError(f"upsample: method is 'reference' or 'resize_blur', got {method!r}")
     if verbose:
         print('>>> upsampling')
     m = torch.as_tensor(anomaly_maps, dtype=torch.float32)
@@ -726,6 +732,8 @@ def upsample(anomaly_maps: Tensor, target_size: int = 256, verbose: bool = True)
         if not torch.cuda.is_available():
             raise RuntimeError("tools.upsample runs on the MI355X HIP kernel only (no CPU fallback)")
         m = m.cuda()
+    if method == 'resize_blur':
+        return ops.resize_gaussian(m.contiguous(), target_size, sigma, border)
     return ops.blur_relu_bilinear(m.contiguous(), 7, target_size)
 
 
@@ -803,14 +811,18 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           seed: int = 0, batch_size: int = 96, projection_training_params=(10, 0.03), fine_tune_params=(30, 0.005),
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
-          localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine'):
+          localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
+          upsample_sigma: float = 4.0):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
     `neighbours`, `localization`, `detector_options` and `metric` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
-    more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns."""
+    more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
+    `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps)."""
+    if upsample_method not in ('reference', 'resize_blur'):
+        raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
@@ -835,7 +847,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         if image_scores is not None:
             image_rows[subject] = image_auroc(out)
         if patch_localization:
-            out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False)      # stays on the device: the Evaluator's GPU metrics
+            out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False, method=upsample_method,
+                                        sigma=upsample_sigma)      # stays on the device: the Evaluator's GPU metrics
         ev = Evaluator(evaluation_metrics=[m for m in metrics if (m != 'f1-score') == patch_localization or m == 'auroc'])
         ev.evaluate(out, subject, sub_out, patch_level=patch_localization)
         rows[subject] = {k: v for k, v in vars(ev.scores).items() if v is not None}
