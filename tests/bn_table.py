@@ -472,40 +472,42 @@ class Arena:
     def _big(self, nbytes):
         return torch.full((nbytes + 2 * GUARD_BYTES,), 255, dtype=torch.uint8, device=self.dev)
 
-    def inp(self, name, t, mutable=False):
+    def inp(self, name, t, mutable=False, lead=0):
+        """lead: the view starts `lead` bytes further into its allocation (a tensor that is not 16-byte aligned); those bytes are guard."""
         if t is None:
             return None
         t = t.contiguous()
         nb = t.numel() * t.element_size()
-        big = self._big(nb)
-        view = big[GUARD_BYTES:GUARD_BYTES + nb].view(t.dtype).view(t.shape)
+        big = self._big(nb + lead)
+        view = big[GUARD_BYTES + lead:GUARD_BYTES + lead + nb].view(t.dtype).view(t.shape)
         view.copy_(t)
-        (self.outs if mutable else self.ins).append((name, big, big.clone() if not mutable else None, nb, t.dtype, True))
+        (self.outs if mutable else self.ins).append((name, big, big.clone() if not mutable else None, nb, t.dtype, True, lead))
         return view
 
-    def out(self, name, shape, dtype, all_written=True):
+    def out(self, name, shape, dtype, all_written=True, lead=0):
         n = 1
         for s in shape:
             n *= s
         nb = n * torch.empty((), dtype=dtype).element_size()
-        big = self._big(nb)
-        self.outs.append((name, big, None, nb, dtype, all_written))
-        return big[GUARD_BYTES:GUARD_BYTES + nb].view(dtype).view(shape)
+        big = self._big(nb + lead)
+        self.outs.append((name, big, None, nb, dtype, all_written, lead))
+        return big[GUARD_BYTES + lead:GUARD_BYTES + lead + nb].view(dtype).view(shape)
 
     def check_outputs(self, rid):
         torch.cuda.synchronize()
-        for name, big, _, nb, dtype, all_written in self.outs:
-            assert bool((big[:GUARD_BYTES] == 255).all()), f"{rid}: the launch wrote in front of `{name}`"
-            assert bool((big[GUARD_BYTES + nb:] == 255).all()), f"{rid}: the launch wrote past the end of `{name}`"
+        for name, big, _, nb, dtype, all_written, lead in self.outs:
+            front = GUARD_BYTES + lead
+            assert bool((big[:front] == 255).all()), f"{rid}: the launch wrote in front of `{name}`"
+            assert bool((big[front + nb:] == 255).all()), f"{rid}: the launch wrote past the end of `{name}`"
             if not all_written:
                 continue
-            body = big[GUARD_BYTES:GUARD_BYTES + nb].view(dtype)
+            body = big[front:front + nb].view(dtype)
             left = int((body == 255).sum()) if dtype == torch.uint8 else int(torch.isnan(body).sum())
             assert left == 0, f"{rid}: {left} elements of `{name}` left unwritten or NaN"
 
     def check_inputs(self, rid):
         torch.cuda.synchronize()
-        for name, big, snap, _, _, _ in self.ins:
+        for name, big, snap, _, _, _, _ in self.ins:
             assert torch.equal(big, snap), f"{rid}: input `{name}` or its guards were written"
 
 
@@ -513,14 +515,16 @@ class Arena:
 WORST = {}
 
 
-def within(rid, kind, got, want, bar):
-    """Prints the worst error / bar of one output, then asserts every element within its bar."""
+def within(rid, kind, got, want, bar, worst_of=None):
+    """Prints the worst error / bar of one output, then asserts every element within its bar.  worst_of: the dict that keeps the worst
+    ratio per kind (default: this table's WORST)."""
     got = got.detach().cpu().double().reshape(want.shape)
     assert bool(torch.isfinite(got).all()), f"{rid}: non-finite values in the output"
     err = (got - want).abs()
     ratio = torch.where(bar > 0, err / bar.clamp(min=1e-300), torch.where(err > 0, float("inf"), 0.0).to(err.dtype))
     worst = float(ratio.max())
-    WORST[kind] = max(WORST.get(kind, 0.0), worst)
+    worst_of = WORST if worst_of is None else worst_of
+    worst_of[kind] = max(worst_of.get(kind, 0.0), worst)
     print(f"   {rid}: worst err / bar {worst:.3f}", flush=True)
     if worst > 1.0:
         i = int(ratio.reshape(-1).argmax())
@@ -528,8 +532,8 @@ def within(rid, kind, got, want, bar):
                              f"{got.reshape(-1)[i].item():.9g}, want {want.reshape(-1)[i].item():.9g}, bar {bar.reshape(-1)[i].item():.3e}")
 
 
-def print_worst():
-    for kind, v in sorted(WORST.items()):
+def print_worst(worst_of=None):
+    for kind, v in sorted((WORST if worst_of is None else worst_of).items()):
         print(f"worst {kind}: err / bar {v:.3f}", flush=True)
 
 
