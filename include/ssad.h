@@ -565,6 +565,26 @@ int ssad_l2_knn_index_split(const float* x, const float* bank, const float* bank
 int ssad_l2_from_dots(const float* sim, const float* qsq, const float* bsq, float* out, int64_t Q, int R, void* stream);
 int ssad_knn_reweight_l2(const float* xs, const float* bank, const int* mstar, const int* nbr, const float* smax, float* out, int64_t Q,
                          int D, int R, int bp, void* stream);
+/* SPADE's image-conditioned gallery for the Euclidean kNN (csrc/knn_gallery.hip; Cohen & Hoshen 2020): a query image is scored against
+ * the rows of K bank images only.  Queries x [Q P][D] and bank [T P][D] hold P rows per image, image after image.
+ * ssad_group_means: out[g][c] = mean_i x[g P + i][c], the image descriptor: summed in fp64 in row order 0 .. P - 1, rounded once to
+ *   fp32 -- an image's descriptor is the same bits in every batch.  G <= 65535.
+ * ssad_l2_direct: out[q][t] = sum_c (q[q][c] - b[t][c])^2 by direct differences (no cancellation), one wave per pair in the order
+ *   of ssad_row_sqnorms (lane-strided fma chain, xor butterfly): a pair's bits do not depend on Q or T.  Q <= 65535.
+ * ssad_l2_knn_gallery / _index: ssad_l2_knn_fused / ssad_l2_knn_index with the bank of query image q restricted to the row blocks
+ *   [g P, (g + 1) P), g = gallery[q][0 .. K - 1] (int32 bank-image ids).  Grid (ceil(P / 128), Q, S): a query tile never straddles two
+ *   images, a bank tile never two blocks.  A (query, bank row) pair gets the bits the whole-bank kernels give it: same tile, K order,
+ *   norms and d2 = fmaxf((qn + bn) - 2 dot, 0).  idx holds GLOBAL bank rows, equal d2 go to the smaller global row.  An entry outside
+ *   0 .. T - 1 is skipped, never dereferenced; a query left with fewer than k candidates gets out = +inf, the missing slots of the
+ *   index form (+inf, -1).  S >= 1 splits the K entries; S > 1 needs part ([S][Q P][3] floats / 64-bit keys, 8-byte aligned) and a
+ *   merge launch.  out, dist and idx are the same bits for every S and on every call.  D % 32 == 0, D <= 65536, k in 1..3,
+ *   K P >= k, Q <= 65535, T P < 2^31. */
+int ssad_group_means(const float* x, float* out, int64_t G, int P, int D, void* stream);
+int ssad_l2_direct(const float* q, const float* b, float* out, int64_t Q, int T, int D, void* stream);
+int ssad_l2_knn_gallery(const float* x, const float* bank, const float* bank_sq, const int* gallery, float* part, float* out, int Q,
+                        int P, int T, int K, int D, int k, int S, void* stream);
+int ssad_l2_knn_gallery_index(const float* x, const float* bank, const float* bank_sq, const int* gallery, void* part, float* dist,
+                              int* idx, int Q, int P, int T, int K, int D, int k, int S, void* stream);
 /* Locally aware patch features from two stage maps of one trunk pass (csrc/patch_features.hip).  Replaces nothing in the reference,
  * which scores 841 windows per image (models.py:211-219); this is the feature construction of PatchCore (Roth et al., CVPR 2022,
  * section 3.1) as anomalib implements it: AvgPool2d(3, 1, 1) of every stage map, F.interpolate(mode='bilinear', align_corners=False)

@@ -59,6 +59,10 @@ SIGNATURES = {
     "ssad_l2_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2_from_dots": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_fp],
     "ssad_knn_reweight_l2": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_group_means": [_c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
+    "ssad_l2_direct": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_gallery": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_gallery_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_local_patch_features": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_coreset_greedy": [_c_fp, _c_l, _c_i, _c_i, _c_l, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_gaussian_fit_stats": [_c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp],

@@ -415,14 +415,19 @@ def check_coreset(coreset, coreset_dim=128):
     return coreset
 
 
-IMAGE_SCORES = (None, 'max', 'reweighted')
+IMAGE_SCORES = (None, 'max', 'reweighted', 'retrieval')
 
 
-def check_image_scores(image_scores, neighbours=9):
-    """ValueError unless `image_scores` is None, 'max' or 'reweighted' and, for 'reweighted', `neighbours` an int in 2..32 (one
-    neighbour gives the weight 0 by the formula)."""
+def check_image_scores(image_scores, neighbours=9, gallery=None):
+    """ValueError unless `image_scores` is None, 'max', 'reweighted' or 'retrieval' and, for 'reweighted', `neighbours` an int in
+    2..32 (one neighbour gives the weight 0 by the formula).  'retrieval' (SPADE's image score) exists with a gallery only, and
+    'reweighted' without one only: the neighbourhood of the nearest bank row is taken over the whole bank."""
     if image_scores not in IMAGE_SCORES:
         raise ValueError(f"image_scores must be one of {IMAGE_SCORES}, got {image_scores!r}")
+    if image_scores == 'retrieval' and gallery is None:
+        raise ValueError("image_scores='retrieval' needs a gallery (gallery=K): it is the mean distance to the K retrieved images")
+    if image_scores == 'reweighted' and gallery is not None:
+        raise ValueError("image_scores='reweighted' does not go with a gallery: its neighbourhood is taken over the whole bank")
     if image_scores == 'reweighted':
         if isinstance(neighbours, (bool, np.bool_)) or not isinstance(neighbours, (int, np.integer)) or not 2 <= neighbours <= 32:
             raise ValueError(f"neighbours must be an int in 2..32 for image_scores='reweighted', got {neighbours!r}")
@@ -444,6 +449,20 @@ def check_metric(metric):
     if metric not in METRICS:
         raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
     return metric
+
+
+def check_gallery(gallery, metric='euclidean', coreset=None):
+    """ValueError unless `gallery` is None or an int K >= 1 (SPADE's number of retrieved images) with metric='euclidean' (SPADE's
+    metric; there is one gallery kernel) and no coreset (a coreset dissolves the image blocks the gallery is made of)."""
+    if gallery is None:
+        return None
+    if isinstance(gallery, (bool, np.bool_)) or not isinstance(gallery, (int, np.integer)) or gallery < 1:
+        raise ValueError(f"gallery must be None or an int K >= 1 (images retrieved per test image), got {gallery!r}")
+    if metric != 'euclidean':
+        raise ValueError(f"gallery needs metric='euclidean' (SPADE's metric; the gallery kernel is Euclidean), got metric={metric!r}")
+    if coreset is not None:
+        raise ValueError("gallery needs coreset=None: a coreset dissolves the image blocks a gallery is made of")
+    return int(gallery)
 
 
 def coreset_select(bank_n, m, coreset_dim=128):
@@ -472,10 +491,19 @@ class AnomalyDetector(Detector):
 
     `metric` (opt-in): 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's: the bank keeps the raw rows plus
     their squared norms `bank_sq`, every distance is sqrt(max(|x|^2 + |b|^2 - 2 <x, b>, 0)) (csrc/knn_l2.hip), the coreset is
-    selected on the raw rows, and the embedding width must be a multiple of 32 (ValueError otherwise: there is no unfused form)."""
+    selected on the raw rows, and the embedding width must be a multiple of 32 (ValueError otherwise: there is no unfused form).
+
+    `gallery` (opt-in; SPADE, Cohen & Hoshen 2020): None = every query meets the whole bank; an int K >= 1 = every query IMAGE is
+    scored against the rows of the K' = min(K, T) bank images nearest to it only (T bank images of `num_patches` rows each).  Stage
+    1: the image descriptor is the mean of an image's rows (ops.group_means -- this project's stand-in for SPADE's pooled
+    last-stage feature), `bank_desc` holds the bank images', the squared distances are taken by direct differences (ops.l2_direct)
+    and the K' nearest are the first columns of a stable ascending sort (equal distances to the smaller image).  Stage 2:
+    ops.l2_knn_gallery (csrc/knn_gallery.hip), the Euclidean kernel on those images' row blocks.  Needs metric='euclidean',
+    coreset=None, patch_level=True with num_patches, whole images everywhere, and for fit(split=True) `groups` with num_patches
+    contiguous rows per image.  image_scores takes 'max' and 'retrieval' (the mean of the K' stage-1 distances), not 'reweighted'."""
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
-                 coreset_dim: int = 128, metric: str = 'cosine') -> None:
+                 coreset_dim: int = 128, metric: str = 'cosine', gallery: int = None) -> None:
         super().__init__(patch_level, batch, num_patches)
         self.k = 3
         self.bank = None
@@ -485,9 +513,39 @@ class AnomalyDetector(Detector):
         self.coreset_dim = coreset_dim
         self.coreset_rows = None        # after fit with a coreset: (sel, rad) -- sel indexes the bank rows after the split
         self.coreset_counts = None      # after fit with a coreset: (rows kept, rows after the split)
+        self.gallery = check_gallery(gallery, self.metric, self.coreset)
+        self.bank_desc = None           # gallery: descriptors of the bank images (ops.group_means)
+        if self.gallery is not None:
+            if not patch_level or not num_patches or int(num_patches) < 1:
+                raise ValueError("gallery needs a patch-level detector (patch_level=True with num_patches): its bank is made of images")
+            self.patches = int(num_patches)
+
+    def _whole_images(self, what, rows: int) -> int:
+        if rows < 1 or rows % self.patches:
+            raise ValueError(f"{what}: with a gallery, {rows} rows are not whole images of {self.patches} patches")
+        return rows // self.patches
+
+    def _check_fit(self, emb, split, groups):
+        if self.gallery is None:
+            return groups
+        n = int(emb.shape[0])
+        self._whole_images("fit", n)
+        if groups is None:
+            if split:
+                raise ValueError("fit: with a gallery, fit(split=True) needs `groups` (the split is drawn over images)")
+            return None
+        g = np.asarray(torch.as_tensor(groups).cpu()).reshape(-1).astype(np.int64)
+        if g.shape[0] != n:
+            raise ValueError(f"groups has {g.shape[0]} entries for {n} rows")
+        blocks = g.reshape(-1, self.patches)
+        if not (blocks == blocks[:, :1]).all() or np.unique(blocks[:, 0]).shape[0] != blocks.shape[0]:
+            raise ValueError(f"fit: with a gallery, every image must have exactly num_patches = {self.patches} contiguous rows")
+        return groups
 
     def _after_bank(self) -> None:
         self.k = 3                      # as the reference's fit sets it; read by _scores for the threshold
+        if self.gallery is not None:
+            self.bank_desc = ops.group_means(self.bank, self.patches)
         if self.coreset is not None:
             r = int(self.bank.shape[0])
             m = coreset_size(self.coreset, r)
@@ -509,6 +567,9 @@ class AnomalyDetector(Detector):
     def fit_bank(self, bank: Tensor) -> None:
         if self.metric == 'euclidean':
             self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
+            if self.gallery is not None:
+                self._whole_images("fit_bank", int(torch.as_tensor(bank).shape[0]))
+                self.bank_desc = None
             self.bank = self._dev(bank)
             self.bank_sq = ops.row_sqnorms(self.bank)
             return
@@ -516,16 +577,43 @@ class AnomalyDetector(Detector):
 
     def state(self):
         """What another rank needs to score like this detector (tools.inference under torch.distributed): the metric and the bank
-        rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel."""
-        return {"metric": self.metric, "bank": self.bank.cpu()}
+        rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel.  With a
+        gallery the state names it (`gallery`: K); `bank_desc` is recomputed like `bank_sq`."""
+        state = {"metric": self.metric, "bank": self.bank.cpu()}
+        if self.gallery is not None:
+            state["gallery"] = self.gallery
+        return state
 
     def load_state(self, state) -> None:
         if state["metric"] != self.metric:
             raise ValueError(f"load_state: the bank was fitted with metric={state['metric']!r}, this detector has {self.metric!r}")
+        if state.get("gallery") != self.gallery:
+            raise ValueError(f"load_state: the bank was fitted with gallery={state.get('gallery')!r}, this detector has {self.gallery!r}")
+        if self.gallery is not None:
+            self._whole_images("load_state", int(state["bank"].shape[0]))
         self.bank = self._dev(state["bank"])
         self.bank_sq = ops.row_sqnorms(self.bank) if self.metric == 'euclidean' else None
+        self.bank_desc = ops.group_means(self.bank, self.patches) if self.gallery is not None else None
+
+    def retrieve(self, x):
+        """Stage 1 of the gallery for the whole query images x [Q * num_patches][D] (on the device): (gallery int32 [Q][K'],
+        d2 float32 [Q][K']), the K' = min(K, T) bank images nearest to each query image by the squared distance between the image
+        descriptors, nearest first, equal distances to the smaller image, and those squared distances."""
+        if self.gallery is None:
+            raise ValueError("retrieve: the detector has no gallery (AnomalyDetector(gallery=K))")
+        self._whole_images("predict", int(x.shape[0]))
+        if self.bank_desc is None:
+            self.bank_desc = ops.group_means(self.bank, self.patches)
+        d2 = ops.l2_direct(ops.group_means(x, self.patches), self.bank_desc)
+        vals, order = torch.sort(d2, dim=1, stable=True)
+        kq = min(self.gallery, int(d2.shape[1]))
+        return order[:, :kq].to(torch.int32).contiguous(), vals[:, :kq].contiguous()
 
     def _scores(self, x):
+        if self.gallery is not None:
+            self._check_width("predict", x.shape[1])
+            gallery, _ = self.retrieve(x)
+            return ops.l2_knn_gallery(x, self.bank, self.bank_sq, gallery, self.patches, self.k)
         if self.metric == 'euclidean':
             self._check_width("predict", x.shape[1])
             return ops.l2_knn_fused(x, self.bank, self.bank_sq, self.k)
@@ -543,20 +631,33 @@ class AnomalyDetector(Detector):
     def kneighbors(self, x: Tensor, k: int = None):
         """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
         idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by the detector's metric, nearest first, equal
-        distances to the smaller row.  idx indexes self.bank (after the split and the coreset).  Works at both levels."""
+        distances to the smaller row.  idx indexes self.bank (after the split and the coreset).  Works at both levels.  With a gallery
+        x holds whole images and the neighbours are taken among the rows of each image's gallery (idx still indexes self.bank)."""
         if self.bank is None:
             raise ValueError("kneighbors: the detector has no bank (fit or fit_bank first)")
         x = self._dev(x)
         if x.shape[1] % 32:
             raise ValueError(f"kneighbors: the index kernel needs an embedding width that is a multiple of 32, got {x.shape[1]}")
-        if self.metric == 'euclidean':
+        if self.gallery is not None:
+            gallery, _ = self.retrieve(x)
+            dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, self.k if k is None else k)
+        elif self.metric == 'euclidean':
             dist, idx = ops.l2_knn_index(x, self.bank, self.bank_sq, self.k if k is None else k)
         else:
             dist, idx = ops.cosine_knn_index(x, self.bank, self.k if k is None else k)
         return dist, idx.long()
 
+    def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = 9, scores: Tensor = None) -> Tensor:
+        """Detector.image_scores; with a gallery also mode='retrieval', SPADE's image score: the mean of the K' stage-1 distances
+        sqrt(d2) between the image's descriptor and those of its retrieved bank images."""
+        if mode == 'retrieval':
+            self._check_image_scores(mode, neighbours)
+            _, d2 = self.retrieve(self._dev(x))
+            return torch.sqrt(d2).mean(1)
+        return super().image_scores(x, mode, neighbours, scores)
+
     def _check_image_scores(self, mode, neighbours) -> None:
-        check_image_scores(mode, neighbours)
+        check_image_scores(mode, neighbours, self.gallery)
         if not self.patch_level or not self.dim:
             raise ValueError("image_scores needs a patch-level detector (patch_level=True with num_patches)")
         if self.bank is None:

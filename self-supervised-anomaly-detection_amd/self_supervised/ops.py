@@ -939,6 +939,103 @@ def knn_reweight_l2(xs, bank, mstar, nbr, smax):
     return out
 
 
+def group_means(x, p):
+    """x [G p][D], p rows per image, image after image -> [G][D] per-image means (csrc/knn_gallery.hip ssad_group_means): summed in
+    fp64 in row order, rounded once to fp32 -- an image's mean is the same bits in every batch.  The gallery's image descriptor."""
+    n, d = x.shape
+    p = int(p)
+    if p < 1 or n < 1 or n % p:
+        raise ValueError(f"group_means: {n} rows are not whole images of {p} rows")
+    g = n // p
+    out = _new((g, d), x)
+    _run("group_means", 1.0 * n * d, 4.0 * (x.numel() + g * d),
+         lambda: _hip.lib().ssad_group_means(_hip.ptr(x), _hip.ptr(out), g, p, d, _hip.stream()))
+    return out
+
+
+def l2_direct(q, b):
+    """q [Q][D], b [T][D] -> [Q][T] SQUARED Euclidean distances sum (q - b)^2 by direct differences (csrc/knn_gallery.hip
+    ssad_l2_direct): no cancellation, a pair's bits do not depend on Q or T."""
+    nq, d = q.shape
+    t = b.shape[0]
+    if b.shape[1] != d or nq < 1 or t < 1:
+        raise ValueError(f"l2_direct: shapes {tuple(q.shape)} and {tuple(b.shape)} do not go together")
+    out = _new((nq, t), q)
+    _run("l2_direct", 3.0 * nq * t * d, 4.0 * (q.numel() + nq * b.numel() + nq * t),
+         lambda: _hip.lib().ssad_l2_direct(_hip.ptr(q), _hip.ptr(b), _hip.ptr(out), nq, t, d, _hip.stream()))
+    return out
+
+
+def gallery_splits(q, p, kk):
+    """Splits S of l2_knn_gallery over the kk gallery entries of q query images of p rows: 1 when the (query tile, image) workgroups
+    alone reach KNN_SPLIT_TARGET_WG, else enough splits to reach that many, at most kk.  SSAD_KNN_SPLIT=0 forces 1.  The results
+    are the same bits for every S."""
+    if os.environ.get("SSAD_KNN_SPLIT", "1") == "0":
+        return 1
+    wgs = -(-int(p) // 128) * int(q)
+    if wgs >= KNN_SPLIT_TARGET_WG:
+        return 1
+    return max(1, min(-(-KNN_SPLIT_TARGET_WG // wgs), int(kk)))
+
+
+def _gallery_args(name, x, bank, bank_sq, gallery, p, k, splits):
+    n, d = x.shape
+    r = bank.shape[0]
+    p, k = int(p), int(k)
+    _check_l2_width(name, d)
+    if bank.shape[1] != d:
+        raise ValueError(f"{name}: the queries have {d} columns, the bank {bank.shape[1]}")
+    if p < 1 or n < 1 or n % p or r < 1 or r % p:
+        raise ValueError(f"{name}: {n} query rows and {r} bank rows are not both whole images of {p} rows")
+    if bank_sq.shape != (r,):
+        raise ValueError(f"{name}: bank_sq must hold one squared norm per bank row ({r}), got {tuple(bank_sq.shape)}")
+    q, t = n // p, r // p
+    if gallery.dim() != 2 or gallery.shape[0] != q or gallery.shape[1] < 1 or gallery.dtype != torch.int32:
+        raise ValueError(f"{name}: gallery must be int32 [{q}][K] with K >= 1, got {gallery.dtype} {tuple(gallery.shape)}")
+    kk = int(gallery.shape[1])
+    if not 1 <= k <= 3:
+        raise ValueError(f"{name}: k must be 1, 2 or 3, got {k}")
+    if kk * p < k:
+        raise ValueError(f"{name}: a gallery of {kk} images of {p} rows has fewer than k = {k} rows")
+    if q > 65535:
+        raise ValueError(f"{name}: at most 65535 query images per call, got {q}")
+    s = gallery_splits(q, p, kk) if splits is None else int(splits)
+    if not 1 <= s <= 65535:
+        raise ValueError(f"{name}: splits must lie in 1..65535, got {s}")
+    return n, d, q, p, t, kk, k, s
+
+
+def l2_knn_gallery(x, bank, bank_sq, gallery, p, k=3, splits=None):
+    """l2_knn_fused with the bank of every query image restricted to a gallery of bank images (SPADE; csrc/knn_gallery.hip
+    ssad_l2_knn_gallery): x [Q p][D] and bank [T p][D] hold p rows per image, image after image; gallery int32 [Q][K] names the K
+    bank images of each query image (an entry outside 0..T-1 is skipped) -> [Q p] mean of the k smallest Euclidean distances to the
+    rows of those images, +inf where fewer than k rows are left.  A (query, bank row) pair gets l2_knn_fused's bits.  `splits`: None =
+    the gallery_splits rule; S >= 1 = that many splits of the K entries; the same bits for every S."""
+    n, d, q, p, t, kk, k, s = _gallery_args("l2_knn_gallery", x, bank, bank_sq, gallery, p, k, splits)
+    out = _new((n,), x)
+    part = _new((s, n, 3), x) if s > 1 else None
+    _run("l2_knn_gallery", 2.0 * n * d * kk * p, 4.0 * (x.numel() + q * kk * p * (d + 1) + n) + (24.0 * part.numel() if s > 1 else 0.0),
+         lambda: _hip.lib().ssad_l2_knn_gallery(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(gallery, dtype=torch.int32),
+                                                _hip.ptr(part, allow_none=True), _hip.ptr(out), q, p, t, kk, d, k, s, _hip.stream()))
+    return out
+
+
+def l2_knn_gallery_index(x, bank, bank_sq, gallery, p, k=3, splits=None):
+    """kneighbors over the galleries of l2_knn_gallery (csrc/knn_gallery.hip ssad_l2_knn_gallery_index): (dist [Q p][k] float32,
+    idx [Q p][k] int32), the k smallest (squared distance, GLOBAL bank row) pairs of every query among its image's gallery rows,
+    ascending, equal ones to the smaller global row; missing slots hold (+inf, -1).  dist holds the bits l2_knn_gallery averages."""
+    n, d, q, p, t, kk, k, s = _gallery_args("l2_knn_gallery_index", x, bank, bank_sq, gallery, p, k, splits)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64) if s > 1 else None      # (squared-distance bits << 32 | row) keys
+    _run("l2_knn_gallery_index", 2.0 * n * d * kk * p,
+         4.0 * (x.numel() + q * kk * p * (d + 1) + 2 * n * k) + (16.0 * part.numel() if s > 1 else 0.0),
+         lambda: _hip.lib().ssad_l2_knn_gallery_index(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(gallery, dtype=torch.int32),
+                                                      _hip.ptr(part, allow_none=True, dtype=torch.int64), _hip.ptr(dist),
+                                                      _hip.ptr(idx, dtype=torch.int32), q, p, t, kk, d, k, s, _hip.stream()))
+    return dist, idx
+
+
 def bilinear_taps(nf, nc):
     """The sample positions csrc/patch_features.hip uses to resample nc positions to nf (F.interpolate's align_corners=False rule in
     integer arithmetic): per destination index i, num = max((2 i + 1) nc - nf, 0), a = num // (2 nf), b = min(a + 1, nc - 1) and the

@@ -19,7 +19,7 @@ from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer, RegionsOutput
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
 from . import models
-from .models import PeraNet, PositionGaussianDetector, check_coreset, check_image_scores, check_metric
+from .models import PeraNet, PositionGaussianDetector, check_coreset, check_gallery, check_image_scores, check_metric
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -400,10 +400,25 @@ def _check_metric(metric, detector):
     return metric
 
 
-def _check_image_scores(image_scores, neighbours, patch_localization, detector):
+def _check_gallery(gallery, detector, metric, patch_localization, bank, coreset):
+    """The gallery option of the kNN detector (models.check_gallery; SPADE): Euclidean, patch level, the whole training set as the bank
+    (the reference bank is ONE image: nothing to retrieve from) and no coreset."""
+    if gallery is None:
+        return None
+    if detector != 'knn':
+        raise ValueError(f"gallery applies to detector='knn' only, got detector={detector!r}")
+    check_gallery(gallery, metric, coreset)
+    if not patch_localization:
+        raise ValueError("gallery needs patch_localization=True: it restricts the patch-level search to the retrieved images")
+    if bank != 'train':
+        raise ValueError("gallery needs bank='train': the reference bank is one image, there is nothing to retrieve from")
+    return int(gallery)
+
+
+def _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery=None):
     """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
     scores and their nearest bank rows, which the image level and the Gaussian do not have."""
-    check_image_scores(image_scores, neighbours)
+    check_image_scores(image_scores, neighbours, gallery)
     if image_scores is not None and not patch_localization:
         raise ValueError("image_scores needs patch_localization=True: the image level scores images already")
     if image_scores is not None and detector == 'gde':
@@ -453,19 +468,23 @@ def _check_padim(detector, patch_localization, localization, bank, detector_opti
     return opts
 
 
-def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options):
+def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options,
+                   gallery=None):
     """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
     _check_detector(detector)
     _check_metric(metric, detector)
     _check_localization(localization, patch_localization)
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, detector)
-    _check_image_scores(image_scores, neighbours, patch_localization, detector)
+    _check_gallery(gallery, detector, metric, patch_localization, bank, coreset)
+    _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
     if coreset is not None:
         det_kw["coreset"] = coreset
     if metric != 'cosine':
         det_kw["metric"] = metric
+    if gallery is not None:
+        det_kw["gallery"] = gallery
     return models.DETECTORS[detector], det_kw
 
 
@@ -666,7 +685,8 @@ def _score_and_gather(detector, output, emb_dev, n_pred, image_scores, neighbour
 def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_inference: bool = True,
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
               coreset=None, image_scores: str = None, neighbours: int = 9,
-              localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine') -> ModelOutputsContainer:
+              localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine',
+              gallery: int = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -687,9 +707,13 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     image_scores='max' (PaDiM's image score) but no coreset.  `detector_options`: {'channels', 'eps', 'seed', 'factor'} of that detector
     ('padim' only).
     `metric`: 'cosine' (default) = the reference's distance; 'euclidean' = PatchCore's Euclidean distance between the raw rows
-    (AnomalyDetector(metric='euclidean'): search, coreset selection and image scores all in that metric); 'knn' only."""
+    (AnomalyDetector(metric='euclidean'): search, coreset selection and image scores all in that metric); 'knn' only.
+    `gallery`: None (default) = every patch meets the whole bank; an int K >= 1 = SPADE's image-conditioned gallery
+    (AnomalyDetector(gallery=K)): every test image is scored against the rows of the K training images nearest to it by the mean
+    of their rows.  Needs detector='knn', metric='euclidean', patch_localization=True, bank='train' and coreset=None; either
+    localization; image_scores 'max' or 'retrieval' (SPADE's image score: the mean distance to the K retrieved images)."""
     cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
-                                 neighbours, detector_options)
+                                 neighbours, detector_options, gallery)
     del TIMELINE[:]
     print('>>> initializing inference')
     plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
@@ -812,18 +836,19 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
-          upsample_sigma: float = 4.0):
+          upsample_sigma: float = 4.0, gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization`, `detector_options` and `metric` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options`, `metric` and `gallery` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
     `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps)."""
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
-    _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options)
+    _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
+                   gallery)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}
@@ -834,6 +859,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw["detector_options"] = detector_options
     if metric != 'cosine':
         score_kw["metric"] = metric
+    if gallery is not None:
+        score_kw["gallery"] = gallery
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
