@@ -598,6 +598,21 @@ int ssad_l2_knn_gallery_index(const float* x, const float* bank, const float* ba
  *   No atomics, fixed summation order: the same bits on every call. */
 int ssad_local_patch_features(const float* fine, const float* coarse, float* out, int64_t N, int Hf, int Wf, int Cf, int Hc, int Wc,
                               int Cc, int rows_per_block, void* stream);
+/* Stage-pyramid rows from two or three stage maps of one trunk pass (csrc/pyramid_features.hip).  Replaces nothing in the reference;
+ * this is the embedding of PaDiM (Defard et al., ICPR 2020; anomalib's PadimModel) and of SPADE's pixel stage: the stage maps as they
+ * are, the coarser ones replicated (nearest neighbour) to the finest grid, channels concatenated, optionally only chosen columns kept.
+ *   m0, m1, m2 [N][H_s][W_s][C_s] NHWC fp32, finest first (stages = 2: m2 is not read); D = C0 + C1 (+ C2);
+ *   sel [d] int32 on the device, strictly increasing entries in [0, D) (the caller checks them), or NULL = all D columns (d == D)
+ *   -> out [N * H0 * W0][d], rows in (n, i, j) order:
+ *   out[(n, i, j)][k] = m_s[n][(i H_s) div H0][(j W_s) div W0][c], s the stage of column sel[k], c its channel there.
+ *   A pure copy with integer source indices (F.interpolate(mode='nearest') where the ratios are integers); a column nobody chose is
+ *   never written.  C_s % 4 == 0, H0 >= H1 >= H2, W0 >= W1 >= W2, any ratio, map sides in 1 .. 32768, stages * W0 + d <= 16384; the
+ *   maps 16-byte aligned, out as well when d % 4 == 0.
+ *   rows_per_block: fine rows of one image a workgroup walks down, 0 = chosen by the library; the result does not depend on it.
+ *   No atomics: the same bits on every call, for every N. */
+int ssad_stage_pyramid_rows(const float* m0, const float* m1, const float* m2, const int* sel, float* out, int64_t N, int stages,
+                            int H0, int W0, int C0, int H1, int W1, int C1, int H2, int W2, int C2, int d, int rows_per_block,
+                            void* stream);
 /* Greedy k-center (farthest-point) coreset of the kNN bank (PatchCore; csrc/coreset.hip; the reference has no coreset) over the
  * rows of p [R][d] (fp32, row-major), squared Euclidean distance sum_j (p[r][j] - p[c][j])^2 summed as a direct sum of squared
  * differences in one fixed order per row.  sel[0] = start; sel[t] = argmax_r min_{s<t} dist(r, sel[s]), ties to the smallest row;

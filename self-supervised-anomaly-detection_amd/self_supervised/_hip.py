@@ -64,6 +64,8 @@ SIGNATURES = {
     "ssad_l2_knn_gallery": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2_knn_gallery_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_local_patch_features": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_stage_pyramid_rows": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
+                                _c_i, _c_fp],
     "ssad_coreset_greedy": [_c_fp, _c_l, _c_i, _c_i, _c_l, _c_i, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_gaussian_fit_stats": [_c_fp, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_mahalanobis_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],

@@ -194,12 +194,18 @@ class PositionGaussianDetector(Detector):
 
     ``factor``: where the P covariances are factored.  'host' (the default): ``position_gaussian_factor`` on copies of the statistics;
     'device': ``ops.position_gaussian_factor``, a batched fp64 Cholesky + triangular inverse kernel on the statistics where they are
-    (channels <= 512) -- the fit never leaves the device."""
+    (channels <= 512) -- the fit never leaves the device.
+
+    ``preselected=True``: the rows already hold the chosen columns and nothing else (the stage pyramid of
+    ``PeraNet.enable_dense_mode(features='pyramid', columns=position_channels(width, channels, seed))`` writes only those): their
+    width must equal `channels`, the kernels get the identity selection and read contiguous rows.  ``width`` (required then) is the
+    number of columns the selection was drawn from; ``sel`` in ``state()`` still records ``position_channels(width, channels, seed)``,
+    so a saved fit says which columns of the full rows it means."""
 
     FACTORS = ('host', 'device')
 
     def __init__(self, patch_level: bool = True, batch: int = None, num_patches: int = None, channels: int = 96, eps: float = 0.01,
-                 seed: int = 0, factor: str = 'host') -> None:
+                 seed: int = 0, factor: str = 'host', preselected: bool = False, width: int = None) -> None:
         if not patch_level or not num_patches:
             raise ValueError("PositionGaussianDetector is a patch-level detector: patch_level=True and num_patches (positions per "
                              "image) are required")
@@ -211,8 +217,17 @@ class PositionGaussianDetector(Detector):
             raise ValueError(f"factor must be one of {self.FACTORS}, got {factor!r}")
         if factor == 'device' and channels > 512:
             raise ValueError(f"factor='device' takes at most 512 channels, got {channels}")
+        if not isinstance(preselected, (bool, np.bool_)):
+            raise ValueError(f"preselected must be a bool, got {preselected!r}")
+        if preselected:
+            if isinstance(width, (bool, np.bool_)) or not isinstance(width, (int, np.integer)):
+                raise ValueError(f"preselected=True needs width, the number of columns the selection was drawn from, got {width!r}")
+            position_channels(int(width), channels, seed)       # channels <= width
+        elif width is not None:
+            raise ValueError("width belongs to preselected=True (otherwise the rows' own width is the one the selection is drawn from)")
         super().__init__(True, batch, num_patches)
         self.factor = factor
+        self.preselected, self.width = bool(preselected), None if width is None else int(width)
         self.num_patches = int(num_patches)
         self.channels, self.eps, self.seed = int(channels), float(eps), int(seed)
         self.sel = self.mu_hi = self.mu_lo = self.w = None
@@ -234,13 +249,27 @@ class PositionGaussianDetector(Detector):
 
     def check_fit_size(self, rows: int, n_images, width: int) -> None:
         self.fit_images(self._images(rows) if n_images is None else n_images)      # the images the 70/30 split keeps
+        self._check_width(width)
         if self.channels > width:
             raise ValueError(f"channels must be a multiple of 32 in 32..{width} (the rows' width), got {self.channels}")
+
+    def _check_width(self, width: int) -> None:
+        if self.preselected and int(width) != self.channels:
+            raise ValueError(f"preselected=True: the rows must hold the {self.channels} chosen columns and nothing else, got {int(width)} "
+                             f"columns")
+
+    def _selection(self, width: int):
+        """(sel recorded in the state, sel the kernels index the rows with)."""
+        if self.preselected:
+            self._check_width(width)
+            return position_channels(self.width, self.channels, self.seed), torch.arange(self.channels, dtype=torch.int64)
+        sel = position_channels(int(width), self.channels, self.seed)
+        return sel, sel
 
     def _check_fit(self, emb, split, groups):
         """groups: image index per row (default: implied by the row order, `num_patches` rows per image)."""
         n_img = self._images(int(emb.shape[0]))
-        position_channels(int(emb.shape[1]), self.channels, self.seed)
+        self._selection(int(emb.shape[1]))
         self.fit_images(n_img, split)
         if not split:
             return groups
@@ -254,11 +283,11 @@ class PositionGaussianDetector(Detector):
     def fit_bank(self, bank: Tensor) -> None:
         bank = torch.as_tensor(bank)
         n_img = self._images(int(bank.shape[0]))
-        sel = position_channels(int(bank.shape[1]), self.channels, self.seed)
+        sel, ksel = self._selection(int(bank.shape[1]))
         self.fit_images(n_img, split=False)
         x = self._dev(bank)
-        sel_dev = ops.position_sel(sel, x.shape[1], x.device)
-        mean, scatter = ops.position_gaussian_fit_stats(x, sel, n_img, self.num_patches, sel_dev=sel_dev)
+        sel_dev = ops.position_sel(ksel, x.shape[1], x.device)
+        mean, scatter = ops.position_gaussian_fit_stats(x, ksel, n_img, self.num_patches, sel_dev=sel_dev)
         if self.factor == 'device':
             fitted = ops.position_gaussian_factor(mean, scatter, n_img, self.eps)       # consumes scatter; nothing visits the host
         else:
@@ -271,7 +300,8 @@ class PositionGaussianDetector(Detector):
         if self.w is None:
             raise ValueError("PositionGaussianDetector: not fitted (fit or fit_bank first)")
         n_img = self._images(int(x.shape[0]))
-        if int(self.sel.max()) >= x.shape[1]:
+        self._check_width(int(x.shape[1]))
+        if not self.preselected and int(self.sel.max()) >= x.shape[1]:
             raise ValueError(f"the rows have {x.shape[1]} columns, the fitted selection reaches column {int(self.sel.max())}")
         return ops.position_mahalanobis(x, self.sel, self.mu_hi, self.mu_lo, self.w, n_img, self.num_patches, sel_dev=self._sel_dev)
 
@@ -285,16 +315,20 @@ class PositionGaussianDetector(Detector):
 
     def state(self) -> dict:
         return {"sel": self.sel.cpu(), "mu_hi": self.mu_hi.cpu(), "mu_lo": self.mu_lo.cpu(), "w": self.w.cpu(), "eps": self.eps,
-                "channels": self.channels, "seed": self.seed, "factor": self.factor}
+                "channels": self.channels, "seed": self.seed, "factor": self.factor, "preselected": self.preselected,
+                "width": self.width}
 
     def load_state(self, state: dict) -> None:
         self.mu_hi, self.mu_lo, self.w = (self._dev(state[k]) for k in ("mu_hi", "mu_lo", "w"))
         self.sel = torch.as_tensor(state["sel"]).cpu().long()
-        self._sel_dev = ops.position_sel(self.sel, int(self.sel.max()) + 1, self.mu_hi.device)
+        self.preselected, self.width = bool(state.get("preselected", False)), state.get("width")
+        ksel = torch.arange(self.sel.numel(), dtype=torch.int64) if self.preselected else self.sel
+        self._sel_dev = ops.position_sel(ksel, int(ksel.max()) + 1, self.mu_hi.device)
 
     @classmethod
     def from_state(cls, state: dict, patch_level: bool = True, batch: int = None, num_patches: int = None):
         det = cls(patch_level=patch_level, batch=batch, num_patches=num_patches, channels=state["channels"], eps=state["eps"],
-                  seed=state.get("seed", 0), factor=state.get("factor", "host"))
+                  seed=state.get("seed", 0), factor=state.get("factor", "host"), preselected=state.get("preselected", False),
+                  width=state.get("width"))
         det.load_state(state)
         return det

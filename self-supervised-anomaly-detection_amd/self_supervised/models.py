@@ -54,6 +54,24 @@ def _warn_random_backbone():
                       RuntimeWarning, stacklevel=3)
 
 
+def _check_columns(columns, width):
+    """`columns` of enable_dense_mode(features='pyramid'): a sorted, duplicate-free integer vector within [0, width) -> int64 tensor on
+    the host.  ValueError for anything else."""
+    try:
+        c = torch.as_tensor(columns).detach().cpu()
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"dense mode: columns must be a vector of integers, got {type(columns).__name__}") from e
+    if c.dim() != 1 or c.numel() == 0 or c.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"dense mode: columns must be a non-empty vector of integers, got dtype {c.dtype}, shape {tuple(c.shape)}")
+    c = c.long()
+    if int(c.min()) < 0 or int(c.max()) >= width:
+        raise ValueError(f"dense mode: columns must lie within [0, {width}) (the width of the stage pyramid), got {int(c.min())}.."
+                         f"{int(c.max())}")
+    if c.numel() > 1 and not bool((c[1:] > c[:-1]).all()):
+        raise ValueError("dense mode: columns must be sorted ascending without duplicates")
+    return c
+
+
 class PeraNet(_Base):
     """src/self_supervised/models.py:21-341."""
 
@@ -84,7 +102,8 @@ class PeraNet(_Base):
 
         self.mvtec = False
         self.patch_level = False
-        self.dense_layers = None        # enable_dense_mode: the two stages whose maps become the patch features
+        self.dense_layers = None        # enable_dense_mode: the stages whose maps become the patch features
+        self.dense_features, self.dense_columns, self._dense_columns_dev = 'local', None, None
         self.num_classes = num_classes
         self.lr = learning_rate
         self.num_epochs = epochs
@@ -139,19 +158,40 @@ class PeraNet(_Base):
     def disable_patch_level_mode(self):
         self.patch_level = False
 
-    def enable_dense_mode(self, layers=('layer2', 'layer3')):
+    DENSE_FEATURES = ('local', 'pyramid')
+
+    def enable_dense_mode(self, layers=('layer2', 'layer3'), features='local', columns=None):
         """Dense feature-map localisation (opt-in; SPADE / PaDiM / PatchCore): in eval mode ``forward`` makes ONE trunk pass per image
         and returns 'latent_space' = the locally aware patch features of the two stage maps `layers` (finer first; two of layer1 ..
         layer3), one row per position of the finer map ([b * Hf * Wf][Cf + Cc], ops.local_patch_features), beside 'classifier' = the
-        image-level logits of the same pass ([b][num_classes]).  Exact fp32 and eval mode only."""
+        image-level logits of the same pass ([b][num_classes]).  Exact fp32 and eval mode only.
+        features='pyramid' (opt-in): PaDiM's and SPADE's embedding instead -- two or three of layer1 .. layer3 in ascending order, the
+        stage maps as they are, the coarser ones replicated to the finest grid, channels concatenated (ops.stage_pyramid_rows;
+        layer1 .. layer3: 448 columns at a quarter of the image's side).  `columns` (pyramid only): a sorted, duplicate-free integer
+        vector within [0, D) -- the rows then hold only those columns, in that order (PaDiM's random dimension reduction, made where
+        the rows are written)."""
+        if features not in self.DENSE_FEATURES:
+            raise ValueError(f"dense mode: features must be one of {self.DENSE_FEATURES}, got {features!r}")
         layers = tuple(layers) if isinstance(layers, (tuple, list)) else (layers,)
         order = ('layer1', 'layer2', 'layer3')
-        if len(layers) != 2 or any(k not in order for k in layers) or order.index(layers[0]) >= order.index(layers[1]):
-            raise ValueError(f"dense mode takes two of {order}, the finer stage first, got {layers!r}")
-        self.dense_layers = layers
+        if features == 'local':
+            if columns is not None:
+                raise ValueError("dense mode: columns applies to features='pyramid' only")
+            if len(layers) != 2 or any(k not in order for k in layers) or order.index(layers[0]) >= order.index(layers[1]):
+                raise ValueError(f"dense mode takes two of {order}, the finer stage first, got {layers!r}")
+        else:
+            idx = [order.index(k) if k in order else -1 for k in layers]
+            if len(layers) not in (2, 3) or min(idx) < 0 or any(a >= b for a, b in zip(idx, idx[1:])):
+                raise ValueError(f"dense mode with features='pyramid' takes two or three of {order} in ascending order, got {layers!r}")
+            if columns is not None:
+                width = sum(c for name, _, c, _ in engine.BLOCKS if name in layers)
+                columns = _check_columns(columns, width)
+        self.dense_layers, self.dense_features, self.dense_columns = layers, features, columns
+        self._dense_columns_dev = None
 
     def disable_dense_mode(self):
         self.dense_layers = None
+        self.dense_features, self.dense_columns, self._dense_columns_dev = 'local', None, None
 
     def enable_mvtec_inference(self) -> None:
         self.mvtec = True
@@ -246,8 +286,8 @@ class PeraNet(_Base):
         return -(-b // -(-b // per_pass))               # equal passes (256 images: 2 x 128 rather than 155 + 101)
 
     def _dense_geometry(self, x):
-        """((Hf, Wf, Cf), (Hc, Wc, Cc)) of the dense mode's two stage maps for the batch x; ValueError for what the mode does not
-        cover -- raised from shapes and switches alone, before anything is launched."""
+        """((H, W, C), ...) of the dense mode's stage maps for the batch x, finest first (two for features='local', two or three for
+        'pyramid'); ValueError for what the mode does not cover -- raised from shapes and switches alone, before anything is launched."""
         if self.patch_level:
             raise ValueError("dense mode and patch-level mode are two localisations: disable one of them")
         if self.training:
@@ -259,20 +299,29 @@ class PeraNet(_Base):
             raise ValueError(f"dense mode needs images of at least 64 x 64 pixels, got {h} x {w} (the reference's resize of smaller "
                              "inputs belongs to the window modes)")
         shapes = engine.stage_shapes(h, w)
-        fine, coarse = shapes[self.dense_layers[0]], shapes[self.dense_layers[1]]
+        stages = tuple(shapes[k] for k in self.dense_layers)
+        fine = stages[0]
         if fine[0] != fine[1]:
             raise ValueError(f"dense mode needs a square {self.dense_layers[0]} map (the detectors reshape scores to dim x dim), "
                              f"got {fine[0]} x {fine[1]} for images of {h} x {w}")
-        return fine, coarse
+        return stages
 
-    def _forward_dense(self, x, fine, coarse):
+    def _forward_dense(self, x, *stages):
         b, _, h, w = x.shape
-        p, d = fine[0] * fine[1], fine[2] + coarse[2]
+        fine = stages[0]
+        pyramid = self.dense_features == 'pyramid'
+        p, d = fine[0] * fine[1], sum(s[2] for s in stages)
+        sel_dev = None
+        if pyramid and self.dense_columns is not None:
+            if self._dense_columns_dev is None or self._dense_columns_dev.device != x.device:
+                self._dense_columns_dev = ops.pyramid_sel(self.dense_columns, d, x.device)
+            sel_dev = self._dense_columns_dev
+            d = int(sel_dev.numel())
         self.batch, self.num_patches = b, p
         plan = self._eval_plan()
         pooled = torch.empty((b, self.concatenator[0].in_features), device=x.device, dtype=torch.float32)
         rows = torch.empty((b * p, d), device=x.device, dtype=torch.float32)        # allocated before the free HBM is read below
-        held = p * fine[2] + coarse[0] * coarse[1] * coarse[2]
+        held = sum(s[0] * s[1] * s[2] for s in stages)                                # every held stage map, floats per sample
         per_pass = self._samples_per_pass(b, 1, h, w, 0, x.device, held)
         i0 = 0
         while i0 < b:
@@ -280,7 +329,10 @@ class PeraNet(_Base):
             try:
                 maps = dict.fromkeys(self.dense_layers)
                 engine.trunk_eval(plan, x[i0:i1], 0, 0, self.layer_outputs, pooled[i0:i1], maps)
-                ops.local_patch_features(maps[self.dense_layers[0]], maps[self.dense_layers[1]], rows[i0 * p:i1 * p])
+                if pyramid:
+                    ops.stage_pyramid_rows([maps[k] for k in self.dense_layers], out=rows[i0 * p:i1 * p], sel_dev=sel_dev)
+                else:
+                    ops.local_patch_features(maps[self.dense_layers[0]], maps[self.dense_layers[1]], rows[i0 * p:i1 * p])
             except torch.cuda.OutOfMemoryError:
                 if per_pass == 1:
                     raise

@@ -1064,6 +1064,64 @@ def local_patch_features(fine, coarse, out=None, rows_per_block=0):
     return out
 
 
+def pyramid_sel(sel, D, device=None):
+    """The column selection of the stage pyramid, checked where it lives (on the host): `sel` [d] integers, strictly increasing, every
+    entry in [0, D) -> an int32 tensor (on `device` when given).  HipExtensionError otherwise, before anything is launched."""
+    s = torch.as_tensor(sel).detach().cpu().reshape(-1)
+    if s.dtype not in (torch.int32, torch.int64) or s.numel() == 0:
+        raise _hip.HipExtensionError(f"pyramid_sel: sel must be a non-empty int32 / int64 vector, got {s.dtype} x {s.numel()}")
+    if int(s.min()) < 0 or int(s.max()) >= int(D):
+        raise _hip.HipExtensionError(f"pyramid_sel: sel has an entry outside [0, {int(D)}) (min {int(s.min())}, max {int(s.max())})")
+    if s.numel() > 1 and not bool((s[1:] > s[:-1]).all()):
+        raise _hip.HipExtensionError("pyramid_sel: sel must be strictly increasing (sorted, no column twice)")
+    s = s.to(torch.int32).contiguous()
+    return s if device is None else s.to(device)
+
+
+def stage_pyramid_rows(maps, sel=None, out=None, sel_dev=None, rows_per_block=0):
+    """Stage-pyramid rows (PaDiM's and SPADE's embedding; csrc/pyramid_features.hip): maps = 2 or 3 NHWC stage maps [N][H_s][W_s][C_s] of
+    one trunk pass, finest first -> [N * H_0 * W_0][d]: out[(n, i, j)][k] = m_s[n][i H_s // H_0][j W_s // W_0][c] for the stage s and
+    channel c of column sel[k] of the concatenation (D = sum C_s columns); a pure copy, F.interpolate(mode='nearest') + cat where the
+    ratios are integers.  sel: host integers, strictly increasing in [0, D), checked here (None: all D columns); sel_dev: its device copy
+    from pyramid_sel, when the caller keeps one.  out: a contiguous buffer of that shape to fill (a row slice of a larger tensor is
+    one).  Bytes: every map read once, every output row written once; columns nobody chose are never written."""
+    maps = list(maps)
+    if len(maps) not in (2, 3):
+        raise _hip.HipExtensionError(f"stage_pyramid_rows: two or three stage maps, finest first, got {len(maps)}")
+    for m in maps:
+        if not (torch.is_tensor(m) and m.dim() == 4 and m.is_cuda and m.dtype == torch.float32 and m.is_contiguous()):
+            raise _hip.HipExtensionError("stage_pyramid_rows: every map must be a contiguous fp32 ROCm tensor [N][H][W][C], got "
+                                         + (f"device={m.device} dtype={m.dtype} shape={tuple(m.shape)}" if torch.is_tensor(m) else repr(type(m))))
+    n = int(maps[0].shape[0])
+    geo = [tuple(int(v) for v in m.shape[1:]) for m in maps]
+    if any(int(m.shape[0]) != n for m in maps) or n < 1:
+        raise _hip.HipExtensionError(f"stage_pyramid_rows: the maps hold {[int(m.shape[0]) for m in maps]} images")
+    if any(c < 4 or c % 4 for _, _, c in geo):
+        raise _hip.HipExtensionError(f"stage_pyramid_rows: channel counts must be positive multiples of 4, got {[g[2] for g in geo]}")
+    if any(min(h, w) < 1 for h, w, _ in geo) or any(a[0] < b[0] or a[1] < b[1] for a, b in zip(geo, geo[1:])):
+        raise _hip.HipExtensionError(f"stage_pyramid_rows: the maps come finest first, got sizes {[g[:2] for g in geo]}")
+    D = sum(c for _, _, c in geo)
+    if sel is None and sel_dev is None:
+        sd, d = None, D
+    else:
+        sd = pyramid_sel(sel, D, maps[0].device) if sel_dev is None else sel_dev
+        if not (sd.is_cuda and sd.dtype == torch.int32 and sd.dim() == 1 and 1 <= sd.numel() <= D):
+            raise _hip.HipExtensionError("stage_pyramid_rows: sel_dev must be the int32 device vector of pyramid_sel")
+        d = int(sd.numel())
+    h0, w0 = geo[0][:2]
+    if out is None:
+        out = _new((n * h0 * w0, d), maps[0])
+    elif tuple(out.shape) != (n * h0 * w0, d):
+        raise _hip.HipExtensionError(f"stage_pyramid_rows: out is {tuple(out.shape)}, expected {(n * h0 * w0, d)}")
+    g = geo + [(0, 0, 0)] * (3 - len(geo))
+    m2 = maps[2] if len(maps) == 3 else None
+    _run("stage_pyramid_rows", 0.0, 4.0 * (sum(m.numel() for m in maps) + out.numel() + (0 if sd is None else d)),
+         lambda: _hip.lib().ssad_stage_pyramid_rows(_hip.ptr(maps[0]), _hip.ptr(maps[1]), _hip.ptr(m2, True),
+                                                    _hip.ptr(sd, True, torch.int32), _hip.ptr(out), n, len(maps), *g[0], *g[1], *g[2], d,
+                                                    rows_per_block, _hip.stream()))
+    return out
+
+
 def gaussian_fit_stats(x, normalize=True):
     """x [N][D] fp32 -> (mean [D], scatter [D][D], m4 [1]) fp64 of its rows (L2-normalised first when `normalize`): the centred
     sufficient statistics of a Ledoit-Wolf Gaussian fit (csrc/gde.hip), deterministic."""

@@ -19,6 +19,7 @@ from . import ops
 from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer, RegionsOutput
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
 from . import models
+from .density import position_channels
 from .models import PeraNet, PositionGaussianDetector, check_coreset, check_gallery, check_image_scores, check_metric
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
@@ -468,17 +469,45 @@ def _check_padim(detector, patch_localization, localization, bank, detector_opti
     return opts
 
 
+DENSE_FEATURES = ('local', 'pyramid')
+PYRAMID_LAYERS = ('layer1', 'layer2', 'layer3')
+PYRAMID_WIDTH = 64 + 128 + 256          # the columns of layer1 .. layer3 side by side
+
+
+def _check_dense_features(dense_features, localization, patch_localization):
+    """'local' = PatchCore's locally aware rows of layer2 and layer3; 'pyramid' = PaDiM's and SPADE's embedding, layer1 .. layer3 as they
+    are at layer1's grid (PeraNet.enable_dense_mode(features='pyramid')): a feature construction of the dense localisation."""
+    if dense_features not in DENSE_FEATURES:
+        raise ValueError(f"dense_features must be one of {DENSE_FEATURES}, got {dense_features!r}")
+    if dense_features == 'pyramid' and not (patch_localization and localization == 'dense'):
+        raise ValueError("dense_features='pyramid' needs patch_localization=True and localization='dense': it is a feature "
+                         "construction of the dense localisation")
+    return dense_features
+
+
+def _pyramid_columns(detector, det_kw):
+    """The columns the model writes with dense_features='pyramid': PaDiM's selection, drawn once from the detector's seed (every rank
+    draws the same one), or None = all of them (the kNN detectors and GDE)."""
+    if detector != 'padim':
+        return None
+    return position_channels(PYRAMID_WIDTH, det_kw.get("channels", 96), det_kw.get("seed", 0))
+
+
 def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options,
-                   gallery=None):
+                   gallery=None, dense_features='local'):
     """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
     _check_detector(detector)
     _check_metric(metric, detector)
     _check_localization(localization, patch_localization)
+    _check_dense_features(dense_features, localization, patch_localization)
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, detector)
     _check_gallery(gallery, detector, metric, patch_localization, bank, coreset)
     _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
+    if dense_features == 'pyramid' and detector == 'padim':
+        det_kw.update(preselected=True, width=PYRAMID_WIDTH)     # the model writes the chosen columns only (_pyramid_columns)
+        _pyramid_columns(detector, det_kw)                       # channels <= 448, before any file is read
     if coreset is not None:
         det_kw["coreset"] = coreset
     if metric != 'cosine':
@@ -560,12 +589,14 @@ def _plan_inputs(dataset_dir, mvtec_inference, whole):
                            bank_item=bank_item, train_files=train_files, my_train=my_train)
 
 
-def _load_model(model_input_dir, patch_localization, localization, prefetch):
+def _load_model(model_input_dir, patch_localization, localization, prefetch, dense_features='local', columns=None):
     try:
         model = PeraNet.load_from_checkpoint(model_input_dir)
         _mark("checkpoint")
         model.eval()
-        if patch_localization and localization == 'dense':
+        if patch_localization and localization == 'dense' and dense_features == 'pyramid':
+            model.enable_dense_mode(PYRAMID_LAYERS, features='pyramid', columns=columns)
+        elif patch_localization and localization == 'dense':
             model.enable_dense_mode()
         elif patch_localization:
             model.enable_patch_level_mode()
@@ -686,7 +717,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
               coreset=None, image_scores: str = None, neighbours: int = 9,
               localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine',
-              gallery: int = None) -> ModelOutputsContainer:
+              dense_features: str = 'local', gallery: int = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -711,15 +742,21 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     `gallery`: None (default) = every patch meets the whole bank; an int K >= 1 = SPADE's image-conditioned gallery
     (AnomalyDetector(gallery=K)): every test image is scored against the rows of the K training images nearest to it by the mean
     of their rows.  Needs detector='knn', metric='euclidean', patch_localization=True, bank='train' and coreset=None; either
-    localization; image_scores 'max' or 'retrieval' (SPADE's image score: the mean distance to the K retrieved images)."""
+    localization; image_scores 'max' or 'retrieval' (SPADE's image score: the mean distance to the K retrieved images).
+    `dense_features`: the rows of localization='dense'.  'local' (default) = the locally aware patch features above; 'pyramid' =
+    PaDiM's and SPADE's embedding: layer1, layer2 and layer3 as they are, the coarser maps replicated to layer1's grid, 448 columns
+    (PeraNet.enable_dense_mode(features='pyramid'): 64 x 64 maps for 256 x 256 images).  With detector='padim' the model writes only
+    the detector's `channels` columns (density.position_channels(448, channels, seed), the same draw on every rank) and the detector
+    reads them as they are (PositionGaussianDetector(preselected=True)); every other detector gets all 448."""
     cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
-                                 neighbours, detector_options, gallery)
+                                 neighbours, detector_options, gallery, dense_features)
     del TIMELINE[:]
     print('>>> initializing inference')
     plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
     print('>>> preparing model')
     _mark("prefetch-started")
-    model, tester = _load_model(model_input_dir, patch_localization, localization, plan.prefetch)
+    columns = _pyramid_columns(detector, det_kw) if dense_features == 'pyramid' else None
+    model, tester = _load_model(model_input_dir, patch_localization, localization, plan.prefetch, dense_features, columns)
     print('>>> preparing datamodule')
     if mvtec_inference:
         model.enable_mvtec_inference()
@@ -836,19 +873,19 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
-          upsample_sigma: float = 4.0, gallery: int = None):
+          upsample_sigma: float = 4.0, dense_features: str = 'local', gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization`, `detector_options`, `metric` and `gallery` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options`, `metric`, `gallery` and `dense_features` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
     `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps)."""
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
-                   gallery)
+                   gallery, dense_features)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}
@@ -861,6 +898,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw["metric"] = metric
     if gallery is not None:
         score_kw["gallery"] = gallery
+    if dense_features != 'local':
+        score_kw["dense_features"] = dense_features
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
