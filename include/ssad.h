@@ -585,6 +585,28 @@ int ssad_l2_knn_gallery(const float* x, const float* bank, const float* bank_sq,
                         int P, int T, int K, int D, int k, int S, void* stream);
 int ssad_l2_knn_gallery_index(const float* x, const float* bank, const float* bank_sq, const int* gallery, void* part, float* dist,
                               int* idx, int Q, int P, int T, int K, int D, int k, int S, void* stream);
+/* An inverted-file (IVF-Flat) index for the Euclidean kNN (csrc/knn_ivf.hip; PatchCore's approximate search, faiss' IndexIVFFlat):
+ * the bank rows are clustered into nlist cells and stored cell after cell (bank [R][D] sorted by cell, offsets [nlist + 1], perm [R]
+ * the original row of every sorted row); a query meets the rows of the cells probes[n][0 .. nprobe - 1] only.
+ * ssad_segment_means: out[g][c] = mean of x[order[i]][c], i = offsets[g] .. offsets[g + 1] - 1 (k-means' update step; order int32
+ *   [N], the rows sorted by cell): summed in fp64 in order's sequence, rounded once to fp32, no atomics -- the same bits on every
+ *   call.  An empty segment leaves out[g] untouched.  nlist <= 65535.
+ * ssad_l2_knn_ivf / _index: ssad_l2_knn_fused / ssad_l2_knn_index over the probed cells.  The work list is made by the caller on
+ *   the device: pairs [N nprobe] = the pair ids n nprobe + j sorted by the cell they name, tiles [3][G] = cell, first pair and number
+ *   of pairs (1 .. 128) of every tile, a tile never straddling two cells; G is an upper bound (N nprobe / 128 + nlist), a tile whose
+ *   cell is outside 0 .. nlist - 1 exits at once.  Launch 1, grid (G): one cell x up to 128 gathered queries per workgroup, the
+ *   128 x 128 tile of ssad_l2_knn_index; part [N nprobe][3] 64-bit keys (squared-distance bits << 32 | original row), 8-byte aligned.
+ *   Launch 2 merges the nprobe triples of every query.  A (query, bank row) pair gets the bits the whole-bank kernels give it,
+ *   whichever tile it falls into; idx holds ORIGINAL rows (perm), equal d2 go to the smaller original row; a probe entry outside
+ *   0 .. nlist - 1 is skipped; slots the probed cells cannot fill hold (+inf, -1), out = +inf.  Every index read from device memory
+ *   is checked before it addresses anything.  D % 32 == 0, D <= 65536, k in 1..3, N nprobe < 2^31, x 16-byte aligned. */
+int ssad_segment_means(const float* x, const int* order, const int* offsets, float* out, int64_t N, int nlist, int D, void* stream);
+int ssad_l2_knn_ivf(const float* x, const float* bank, const float* bank_sq, const int* offsets, const int* perm, const int* probes,
+                    const int* tiles, const int* pairs, void* part, float* out, int64_t N, int D, int R, int nlist, int nprobe, int G,
+                    int k, void* stream);
+int ssad_l2_knn_ivf_index(const float* x, const float* bank, const float* bank_sq, const int* offsets, const int* perm, const int* probes,
+                          const int* tiles, const int* pairs, void* part, float* dist, int* idx, int64_t N, int D, int R, int nlist,
+                          int nprobe, int G, int k, void* stream);
 /* Locally aware patch features from two stage maps of one trunk pass (csrc/patch_features.hip).  Replaces nothing in the reference,
  * which scores 841 windows per image (models.py:211-219); this is the feature construction of PatchCore (Roth et al., CVPR 2022,
  * section 3.1) as anomalib implements it: AvgPool2d(3, 1, 1) of every stage map, F.interpolate(mode='bilinear', align_corners=False)

@@ -470,12 +470,16 @@ def check_coreset(coreset, coreset_dim=128):
 IMAGE_SCORES = (None, 'max', 'reweighted', 'retrieval')
 
 
-def check_image_scores(image_scores, neighbours=9, gallery=None):
+def check_image_scores(image_scores, neighbours=9, gallery=None, index='flat'):
     """ValueError unless `image_scores` is None, 'max', 'reweighted' or 'retrieval' and, for 'reweighted', `neighbours` an int in
     2..32 (one neighbour gives the weight 0 by the formula).  'retrieval' (SPADE's image score) exists with a gallery only, and
-    'reweighted' without one only: the neighbourhood of the nearest bank row is taken over the whole bank."""
+    'reweighted' without one only: the neighbourhood of the nearest bank row is taken over the whole bank.  With index='ivf' only
+    'max' exists: 'reweighted' would search the whole bank again, which the index is there to avoid."""
     if image_scores not in IMAGE_SCORES:
         raise ValueError(f"image_scores must be one of {IMAGE_SCORES}, got {image_scores!r}")
+    if index == 'ivf' and image_scores in ('reweighted', 'retrieval'):
+        raise ValueError(f"image_scores={image_scores!r} does not go with index='ivf': 'reweighted' takes its neighbourhood over the "
+                         "whole bank and 'retrieval' needs a gallery; index='ivf' takes image_scores='max'")
     if image_scores == 'retrieval' and gallery is None:
         raise ValueError("image_scores='retrieval' needs a gallery (gallery=K): it is the mean distance to the K retrieved images")
     if image_scores == 'reweighted' and gallery is not None:
@@ -517,6 +521,43 @@ def check_gallery(gallery, metric='euclidean', coreset=None):
     return int(gallery)
 
 
+INDEXES = ('flat', 'ivf')
+IVF_OPTIONS = ('iters', 'seed', 'train_rows')
+IVF_MAX_NLIST = 4096
+
+
+def check_index(index, nlist=None, nprobe=8, index_options=None, metric='euclidean', gallery=None):
+    """ValueError unless `index` is 'flat' (the exact search) or 'ivf' (an inverted file over the bank rows: ops.kmeans_l2 cells,
+    ops.l2_knn_ivf) with metric='euclidean' (the index kernel is Euclidean) and no gallery (a gallery already restricts the bank),
+    `nlist` None or an int in 1..4096, `nprobe` an int >= 1 and `index_options` None or a dict with keys among IVF_OPTIONS.
+    With 'flat' the three options must keep their defaults."""
+    if index not in INDEXES:
+        raise ValueError(f"index must be one of {INDEXES}, got {index!r}")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if nlist is not None and not (is_int(nlist) and 1 <= nlist <= IVF_MAX_NLIST):
+        raise ValueError(f"nlist must be None or an int in 1..{IVF_MAX_NLIST}, got {nlist!r}")
+    if not (is_int(nprobe) and nprobe >= 1):
+        raise ValueError(f"nprobe must be an int >= 1, got {nprobe!r}")
+    if index_options is not None and (not isinstance(index_options, dict) or any(k not in IVF_OPTIONS for k in index_options)):
+        raise ValueError(f"index_options must be a dict with keys among {IVF_OPTIONS}, got {index_options!r}")
+    if index == 'flat':
+        if nlist is not None or index_options is not None:
+            raise ValueError("nlist and index_options apply to index='ivf' only")
+        return index
+    if metric != 'euclidean':
+        raise ValueError(f"index='ivf' needs metric='euclidean' (the index kernel is Euclidean), got metric={metric!r}")
+    if gallery is not None:
+        raise ValueError("index='ivf' needs gallery=None: a gallery already restricts the bank of every query image")
+    return index
+
+
+def ivf_nlist(nlist, rows):
+    """Cells of an inverted file over `rows` bank rows: `nlist` itself, or for None ceil(sqrt(rows)) clamped to 1..4096."""
+    if nlist is not None:
+        return int(nlist)
+    return int(min(max(int(np.ceil(np.sqrt(int(rows)))), 1), IVF_MAX_NLIST))
+
+
 def coreset_select(bank_n, m, coreset_dim=128):
     """Greedy k-center coreset of the bank rows bank_n [R][D] as the detector keeps them (L2-normalised with metric='cosine', raw
     with 'euclidean'; PatchCore): the selection runs on bank_n Omega
@@ -552,10 +593,21 @@ class AnomalyDetector(Detector):
     and the K' nearest are the first columns of a stable ascending sort (equal distances to the smaller image).  Stage 2:
     ops.l2_knn_gallery (csrc/knn_gallery.hip), the Euclidean kernel on those images' row blocks.  Needs metric='euclidean',
     coreset=None, patch_level=True with num_patches, whole images everywhere, and for fit(split=True) `groups` with num_patches
-    contiguous rows per image.  image_scores takes 'max' and 'retrieval' (the mean of the K' stage-1 distances), not 'reweighted'."""
+    contiguous rows per image.  image_scores takes 'max' and 'retrieval' (the mean of the K' stage-1 distances), not 'reweighted'.
+
+    `index` (opt-in; PatchCore's approximate search, faiss' IndexIVFFlat): 'flat' (default) = every query meets every bank row;
+    'ivf' = an inverted file.  ``fit`` clusters the bank rows left after the split and the coreset into `nlist` cells (ops.kmeans_l2;
+    None: ceil(sqrt(R)) clamped to 1..4096; `index_options` = {'iters', 'seed', 'train_rows'} of the k-means) and keeps the bank
+    SORTED BY CELL: `bank[i]` is the caller's row `ivf['perm'][i]`, cell c the rows `ivf['offsets'][c] .. ivf['offsets'][c + 1] - 1`.
+    A query meets the rows of the `nprobe` (clamped to nlist) cells whose centroids are nearest (ops.ivf_probes, ops.l2_knn_ivf):
+    the search is APPROXIMATE for nprobe < nlist -- a score is never smaller than the exact one -- and exact, bit for bit, for
+    nprobe = nlist.  The threshold goes through the same search.  ``kneighbors`` returns the caller's rows (before the sort); a
+    slot the probed cells cannot fill is (+inf, -1).  Needs metric='euclidean' and gallery=None; works at both levels and with a
+    coreset.  image_scores takes 'max' only: 'reweighted' and 'retrieval' raise."""
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
-                 coreset_dim: int = 128, metric: str = 'cosine', gallery: int = None) -> None:
+                 coreset_dim: int = 128, metric: str = 'cosine', index: str = 'flat', nlist: int = None, nprobe: int = 8,
+                 index_options: dict = None, gallery: int = None) -> None:
         super().__init__(patch_level, batch, num_patches)
         self.k = 3
         self.bank = None
@@ -571,6 +623,11 @@ class AnomalyDetector(Detector):
             if not patch_level or not num_patches or int(num_patches) < 1:
                 raise ValueError("gallery needs a patch-level detector (patch_level=True with num_patches): its bank is made of images")
             self.patches = int(num_patches)
+        self.index = check_index(index, nlist, nprobe, index_options, self.metric, self.gallery)
+        self.nlist = None if nlist is None else int(nlist)
+        self.nprobe = int(nprobe)
+        self.index_options = dict(index_options or {})
+        self.ivf = None                 # index='ivf' after fit: perm, offsets, centroids, cent_sq, nlist, nprobe (bank: sorted by cell)
 
     def _whole_images(self, what, rows: int) -> int:
         if rows < 1 or rows % self.patches:
@@ -608,15 +665,40 @@ class AnomalyDetector(Detector):
                     self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
                 self.coreset_rows = (sel, rad)
             self.coreset_counts = (int(self.bank.shape[0]), r)
+        if self.index == 'ivf':
+            self._build_index()
+
+    def _build_index(self) -> None:
+        """Clusters the bank rows and re-stores them cell after cell (stable in the caller's row order within a cell)."""
+        r = int(self.bank.shape[0])
+        nlist = ivf_nlist(self.nlist, r)
+        centroids, assign = ops.kmeans_l2(self.bank, nlist, **self.index_options)
+        sorted_cells, perm = torch.sort(assign, stable=True)
+        self.bank = self.bank.index_select(0, perm).contiguous()
+        self.bank_sq = ops.row_sqnorms(self.bank)
+        self._set_index(perm.to(torch.int32), ops.cell_offsets(sorted_cells, nlist), centroids, nlist, min(self.nprobe, nlist))
+
+    def _set_index(self, perm, offsets, centroids, nlist, nprobe) -> None:
+        self.ivf = {"perm": perm.contiguous(), "offsets": offsets.contiguous(), "centroids": centroids.contiguous(),
+                    "cent_sq": ops.row_sqnorms(centroids), "nlist": int(nlist), "nprobe": int(nprobe)}
+
+    def _probes(self, x):
+        return ops.ivf_probes(x, self.ivf["centroids"], self.ivf["cent_sq"], self.ivf["nprobe"])
 
     def describe_fit(self):
-        return None if self.coreset_counts is None else f' coreset: {self.coreset_counts[0]} of {self.coreset_counts[1]} rows'
+        lines = [] if self.coreset_counts is None else [f' coreset: {self.coreset_counts[0]} of {self.coreset_counts[1]} rows']
+        if self.ivf is not None:
+            sizes = (self.ivf["offsets"][1:] - self.ivf["offsets"][:-1]).cpu().numpy()
+            lines.append(f' ivf index: nlist {self.ivf["nlist"]}, nprobe {self.ivf["nprobe"]}, cells of {int(sizes.min())} / '
+                         f'{int(np.median(sizes))} / {int(sizes.max())} rows (smallest / median / largest), {int((sizes == 0).sum())} empty')
+        return '\n'.join(lines) if lines else None
 
     def _check_width(self, what, d):
         if d % 32:
             raise ValueError(f"{what}: metric='euclidean' needs an embedding width that is a multiple of 32, got {d}")
 
     def fit_bank(self, bank: Tensor) -> None:
+        self.ivf = None                 # the rows as given: an index is built by fit (_after_bank) or arrives with load_state
         if self.metric == 'euclidean':
             self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
             if self.gallery is not None:
@@ -630,10 +712,16 @@ class AnomalyDetector(Detector):
     def state(self):
         """What another rank needs to score like this detector (tools.inference under torch.distributed): the metric and the bank
         rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel.  With a
-        gallery the state names it (`gallery`: K); `bank_desc` is recomputed like `bank_sq`."""
+        gallery the state names it (`gallery`: K); `bank_desc` is recomputed like `bank_sq`.  With index='ivf' `bank` is the bank
+        sorted by cell and the state also carries `perm`, `offsets`, `centroids`, `nlist` and `nprobe`."""
         state = {"metric": self.metric, "bank": self.bank.cpu()}
         if self.gallery is not None:
             state["gallery"] = self.gallery
+        if self.index == 'ivf':
+            if self.ivf is None:
+                raise ValueError("state: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
+            state.update({k: self.ivf[k].cpu() for k in ("perm", "offsets", "centroids")}, nlist=self.ivf["nlist"],
+                         nprobe=self.ivf["nprobe"])
         return state
 
     def load_state(self, state) -> None:
@@ -646,6 +734,13 @@ class AnomalyDetector(Detector):
         self.bank = self._dev(state["bank"])
         self.bank_sq = ops.row_sqnorms(self.bank) if self.metric == 'euclidean' else None
         self.bank_desc = ops.group_means(self.bank, self.patches) if self.gallery is not None else None
+        if ("nlist" in state) != (self.index == 'ivf'):
+            raise ValueError(f"load_state: the bank was fitted with index={'ivf' if 'nlist' in state else 'flat'!r}, this detector has "
+                             f"{self.index!r}")
+        self.ivf = None
+        if self.index == 'ivf':
+            dev = self.bank.device
+            self._set_index(state["perm"].to(dev), state["offsets"].to(dev), state["centroids"].to(dev), state["nlist"], state["nprobe"])
 
     def retrieve(self, x):
         """Stage 1 of the gallery for the whole query images x [Q * num_patches][D] (on the device): (gallery int32 [Q][K'],
@@ -666,6 +761,11 @@ class AnomalyDetector(Detector):
             self._check_width("predict", x.shape[1])
             gallery, _ = self.retrieve(x)
             return ops.l2_knn_gallery(x, self.bank, self.bank_sq, gallery, self.patches, self.k)
+        if self.index == 'ivf':
+            self._check_width("predict", x.shape[1])
+            if self.ivf is None:
+                raise ValueError("predict: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
+            return ops.l2_knn_ivf(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"], self.k)
         if self.metric == 'euclidean':
             self._check_width("predict", x.shape[1])
             return ops.l2_knn_fused(x, self.bank, self.bank_sq, self.k)
@@ -684,7 +784,9 @@ class AnomalyDetector(Detector):
         """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
         idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by the detector's metric, nearest first, equal
         distances to the smaller row.  idx indexes self.bank (after the split and the coreset).  Works at both levels.  With a gallery
-        x holds whole images and the neighbours are taken among the rows of each image's gallery (idx still indexes self.bank)."""
+        x holds whole images and the neighbours are taken among the rows of each image's gallery (idx still indexes self.bank).
+        With index='ivf' the neighbours are taken among the rows of the probed cells and idx holds the caller's rows, as index='flat'
+        numbers them (self.bank[i] is row self.ivf['perm'][i]); a slot the cells cannot fill is (+inf, -1)."""
         if self.bank is None:
             raise ValueError("kneighbors: the detector has no bank (fit or fit_bank first)")
         x = self._dev(x)
@@ -693,6 +795,11 @@ class AnomalyDetector(Detector):
         if self.gallery is not None:
             gallery, _ = self.retrieve(x)
             dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, self.k if k is None else k)
+        elif self.index == 'ivf':
+            if self.ivf is None:
+                raise ValueError("kneighbors: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
+            dist, idx = ops.l2_knn_ivf_index(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"],
+                                             self.k if k is None else k)
         elif self.metric == 'euclidean':
             dist, idx = ops.l2_knn_index(x, self.bank, self.bank_sq, self.k if k is None else k)
         else:
@@ -709,7 +816,7 @@ class AnomalyDetector(Detector):
         return super().image_scores(x, mode, neighbours, scores)
 
     def _check_image_scores(self, mode, neighbours) -> None:
-        check_image_scores(mode, neighbours, self.gallery)
+        check_image_scores(mode, neighbours, self.gallery, self.index)
         if not self.patch_level or not self.dim:
             raise ValueError("image_scores needs a patch-level detector (patch_level=True with num_patches)")
         if self.bank is None:

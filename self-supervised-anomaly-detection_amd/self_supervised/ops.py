@@ -1036,6 +1036,200 @@ def l2_knn_gallery_index(x, bank, bank_sq, gallery, p, k=3, splits=None):
     return dist, idx
 
 
+def segment_means(x, order, offsets, out=None):
+    """k-means' update step (csrc/knn_ivf.hip ssad_segment_means): x [N][D], order int32 [N] = the rows sorted by cell, offsets int32
+    [nlist + 1] -> [nlist][D], row g the mean of x[order[offsets[g] : offsets[g + 1]]], summed in fp64 in order's sequence and rounded
+    once to fp32: no atomics, the same bits on every call.  group_means for groups of any length.  An empty segment leaves its row of
+    `out` untouched: pass the previous centroids (None: zeros)."""
+    n, d = x.shape
+    if order.dtype != torch.int32 or tuple(order.shape) != (n,):
+        raise ValueError(f"segment_means: order must be int32 [{n}], got {order.dtype} {tuple(order.shape)}")
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise ValueError(f"segment_means: offsets must be int32 [nlist + 1], got {offsets.dtype} {tuple(offsets.shape)}")
+    nlist = int(offsets.shape[0]) - 1
+    if n < 1 or nlist > 65535:
+        raise ValueError(f"segment_means: needs at least one row and at most 65535 segments, got {n} rows and {nlist} segments")
+    if out is None:
+        out = torch.zeros((nlist, d), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (nlist, d):
+        raise ValueError(f"segment_means: out must be [{nlist}][{d}], got {tuple(out.shape)}")
+    i32 = torch.int32
+    _run("segment_means", 1.0 * n * d, 4.0 * (x.numel() + n + nlist * d),
+         lambda: _hip.lib().ssad_segment_means(_hip.ptr(x), _hip.ptr(order, dtype=i32), _hip.ptr(offsets, dtype=i32), _hip.ptr(out), n,
+                                               nlist, d, _hip.stream()))
+    return out
+
+
+def cell_offsets(sorted_cells, nlist):
+    """Ascending cell numbers [M] (any integer type, on the device) -> int32 [nlist + 1], the first position of every cell and M:
+    cell c holds the positions offsets[c] .. offsets[c + 1] - 1.  A binary search on the device, no synchronisation."""
+    edges = torch.arange(int(nlist) + 1, device=sorted_cells.device, dtype=sorted_cells.dtype)
+    return torch.searchsorted(sorted_cells, edges).to(torch.int32)
+
+
+def ivf_schedule(probes, nlist):
+    """The work list of l2_knn_ivf for probes int32 [N][nprobe], made on the device without a synchronisation: (tiles int32 [3][G],
+    pairs int32 [N nprobe]).  pairs = the pair ids n nprobe + j in a stable sort by the cell they name (entries outside 0..nlist-1
+    last, in no tile); a cell's run is cut into tiles of 128 pairs; tiles[0] = the cell, tiles[1] = the first position in `pairs`,
+    tiles[2] = the pairs of the tile.  G = ceil(N nprobe / 128) + nlist bounds the tiles of any probes; the surplus ones name cell
+    nlist."""
+    n, nprobe = probes.shape
+    nlist = int(nlist)
+    m = n * nprobe
+    g = -(-m // 128) + nlist
+    flat = probes.reshape(-1)
+    cells = torch.where((flat >= 0) & (flat < nlist), flat, torch.full_like(flat, nlist))
+    sorted_cells, pairs = torch.sort(cells, stable=True)
+    start = cell_offsets(sorted_cells, nlist).long()                    # [nlist + 1]
+    tiles_of = (start[1:] - start[:-1] + 127) // 128                    # tiles of every cell
+    last = torch.cumsum(tiles_of, 0)                                    # one past the last tile of every cell
+    t = torch.arange(g, device=probes.device)
+    cell = torch.searchsorted(last, t, right=True)                      # nlist for a surplus tile
+    safe = cell.clamp(max=nlist - 1)
+    first = start[safe] + (t - (last[safe] - tiles_of[safe])) * 128
+    count = (start[safe + 1] - first).clamp(min=0, max=128)
+    tiles = torch.stack([cell, first, count]).to(torch.int32).contiguous()
+    return tiles, pairs.to(torch.int32)
+
+
+def _ivf_args(name, x, bank_sorted, bank_sq, offsets, probes, perm, k):
+    n, d = x.shape
+    r = bank_sorted.shape[0]
+    k = int(k)
+    _check_l2_width(name, d)
+    i32 = torch.int32
+    if bank_sorted.shape[1] != d:
+        raise ValueError(f"{name}: the queries have {d} columns, the bank {bank_sorted.shape[1]}")
+    if n < 1 or r < 1:
+        raise ValueError(f"{name}: needs at least one query and one bank row, got {n} and {r}")
+    if bank_sq.shape != (r,):
+        raise ValueError(f"{name}: bank_sq must hold one squared norm per bank row ({r}), got {tuple(bank_sq.shape)}")
+    if perm.dtype != i32 or tuple(perm.shape) != (r,):
+        raise ValueError(f"{name}: perm must be int32 [{r}] (the original row of every sorted row), got {perm.dtype} {tuple(perm.shape)}")
+    if offsets.dtype != i32 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise ValueError(f"{name}: offsets must be int32 [nlist + 1], got {offsets.dtype} {tuple(offsets.shape)}")
+    nlist = int(offsets.shape[0]) - 1
+    if probes.dtype != i32 or probes.dim() != 2 or probes.shape[0] != n or probes.shape[1] < 1:
+        raise ValueError(f"{name}: probes must be int32 [{n}][nprobe] with nprobe >= 1, got {probes.dtype} {tuple(probes.shape)}")
+    nprobe = int(probes.shape[1])
+    if not 1 <= k <= 3:
+        raise ValueError(f"{name}: k must be 1, 2 or 3, got {k}")
+    if n * nprobe > 2 ** 31 - 1:
+        raise ValueError(f"{name}: {n} queries x {nprobe} probes are too many pairs for one call")
+    if x.data_ptr() % 16:
+        raise ValueError(f"{name}: the queries must start at a 16-byte boundary")
+    return n, d, r, nlist, nprobe, k
+
+
+def _ivf_launch(name, entry, outs, x, bank_sorted, bank_sq, offsets, probes, perm, n, d, r, nlist, nprobe, k):
+    i32 = torch.int32
+    probes = probes.contiguous()
+    tiles, pairs = ivf_schedule(probes, nlist)
+    g = int(tiles.shape[1])
+    part = torch.empty((n * nprobe, 3), device=x.device, dtype=torch.int64)     # (squared-distance bits << 32 | original row) keys
+    # the arithmetic of the expected work (every query meets nprobe cells of R / nlist rows); the kernel issues whole 128 x 128 tiles
+    flops = 2.0 * n * d * nprobe * r / nlist
+    _run(name, flops, 4.0 * (x.numel() * nprobe + bank_sorted.numel() + 2 * r) + 24.0 * part.numel() * 2,
+         lambda: entry(_hip.ptr(x), _hip.ptr(bank_sorted), _hip.ptr(bank_sq), _hip.ptr(offsets, dtype=i32), _hip.ptr(perm, dtype=i32),
+                       _hip.ptr(probes, dtype=i32), _hip.ptr(tiles, dtype=i32), _hip.ptr(pairs, dtype=i32),
+                       _hip.ptr(part, dtype=torch.int64), *outs, n, d, r, nlist, nprobe, g, k, _hip.stream()))
+
+
+def l2_knn_ivf_index(x, bank_sorted, bank_sq, offsets, probes, perm, k=3):
+    """kneighbors over an inverted file (csrc/knn_ivf.hip ssad_l2_knn_ivf_index): x [N][D]; bank_sorted [R][D] the bank rows stored
+    cell after cell, bank_sq their squared norms, offsets int32 [nlist + 1] the cells' bounds, perm int32 [R] the original row of
+    every sorted row; probes int32 [N][nprobe] the cells every query meets (an entry outside 0..nlist-1 is skipped, a cell named
+    twice counts once) -> (dist [N][k] float32, idx [N][k] int32): the k (1..3) smallest (squared distance, ORIGINAL bank row) pairs
+    among the rows of those cells, ascending, equal ones to the smaller original row; slots the cells cannot fill hold (+inf, -1).
+    A (query, bank row) pair gets l2_knn_index's bits, however the pairs fall into tiles.  The work list (ivf_schedule) is made on the
+    device: no host synchronisation."""
+    n, d, r, nlist, nprobe, k = _ivf_args("l2_knn_ivf_index", x, bank_sorted, bank_sq, offsets, probes, perm, k)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    _ivf_launch("l2_knn_ivf_index", _hip.lib().ssad_l2_knn_ivf_index, (_hip.ptr(dist), _hip.ptr(idx, dtype=torch.int32)), x, bank_sorted,
+                bank_sq, offsets, probes, perm, n, d, r, nlist, nprobe, k)
+    return dist, idx
+
+
+def l2_knn_ivf(x, bank_sorted, bank_sq, offsets, probes, perm, k=3):
+    """l2_knn_fused over an inverted file (csrc/knn_ivf.hip ssad_l2_knn_ivf; arguments as l2_knn_ivf_index) -> [N] mean of the k
+    smallest Euclidean distances to the rows of the probed cells, +inf where they hold fewer than k rows: l2_knn_ivf_index's
+    distances averaged, bit for bit."""
+    n, d, r, nlist, nprobe, k = _ivf_args("l2_knn_ivf", x, bank_sorted, bank_sq, offsets, probes, perm, k)
+    out = _new((n,), x)
+    _ivf_launch("l2_knn_ivf", _hip.lib().ssad_l2_knn_ivf, (_hip.ptr(out),), x, bank_sorted, bank_sq, offsets, probes, perm, n, d, r, nlist,
+                nprobe, k)
+    return out
+
+
+IVF_PROBE_CHUNK = 65535         # queries per pass of ivf_probes (the grid bound of l2_from_dots)
+
+
+def ivf_probes(x, centroids, cent_sq, nprobe):
+    """The coarse step of the inverted file: x [N][D], centroids [nlist][D], cent_sq = row_sqnorms(centroids) -> int32 [N][nprobe], the
+    nprobe cells whose centroids are nearest to every query by the kernels' squared distance max(|x|^2 + |c|^2 - 2 <x, c>, 0),
+    ordered by (squared distance, cell): equal distances to the smaller cell.  One GEMM (linear_fwd), l2_from_dots and a selection of
+    packed (distance bits << 32 | cell) keys per pass of IVF_PROBE_CHUNK queries; no host synchronisation."""
+    n = x.shape[0]
+    nlist = int(centroids.shape[0])
+    nprobe = int(nprobe)
+    if not 1 <= nprobe <= nlist:
+        raise ValueError(f"ivf_probes: nprobe must lie in 1..nlist = {nlist}, got {nprobe}")
+    out = torch.empty((n, nprobe), device=x.device, dtype=torch.int32)
+    cells = torch.arange(nlist, device=x.device, dtype=torch.int64)
+    xsq = row_sqnorms(x)
+    for i in range(0, n, IVF_PROBE_CHUNK):
+        xs = x[i:i + IVF_PROBE_CHUNK]
+        d2 = l2_from_dots(linear_fwd(xs, centroids), xsq[i:i + IVF_PROBE_CHUNK], cent_sq)
+        keys = (d2.view(torch.int32).long() << 32) | cells                  # d2 >= 0: the keys order like (d2, cell)
+        out[i:i + IVF_PROBE_CHUNK] = torch.topk(keys, nprobe, dim=1, largest=False, sorted=True).values.bitwise_and_(0xffffffff)
+    return out
+
+
+KMEANS_ROWS_PER_CELL = 256      # rows per cell the iterations are run on at the most (faiss' max_points_per_centroid)
+
+
+def kmeans_init(n, nlist, seed=0, train_rows=None):
+    """The draws of kmeans_l2 for n rows, from a dedicated CPU torch.Generator seeded with `seed` (never the global generators; the
+    same on every rank): (sample, init).  sample: None when the iterations use every row, else the int64 rows they use, ascending
+    -- min(n, train_rows) of them, train_rows=None meaning KMEANS_ROWS_PER_CELL * nlist; init: int64 [nlist] distinct positions in
+    the rows the iterations use, the initial centroids."""
+    n, nlist = int(n), int(nlist)
+    if nlist < 1 or nlist > n:
+        raise ValueError(f"kmeans_l2: nlist must lie in 1..{n} (the rows), got {nlist}")
+    cap = KMEANS_ROWS_PER_CELL * nlist if train_rows is None else int(train_rows)
+    if cap < nlist:
+        raise ValueError(f"kmeans_l2: train_rows must be at least nlist = {nlist}, got {cap}")
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    sample = None
+    if cap < n:
+        sample = torch.randperm(n, generator=g)[:cap].sort().values
+    init = torch.randperm(n if sample is None else cap, generator=g)[:nlist]
+    return sample, init
+
+
+def kmeans_l2(x, nlist, iters=10, seed=0, train_rows=None):
+    """Lloyd's k-means in the Euclidean metric on the device: x [N][D] -> (centroids [nlist][D] float32, assign int32 [N]).  Initial
+    centroids: nlist distinct rows (kmeans_init).  Every iteration: the nearest centroid of every row (l2_knn_index, k = 1: equal
+    distances to the smaller cell), a stable sort of the assignments, segment_means; a cell that loses all its rows keeps its
+    centroid and may stay empty.  The iterations run on at most train_rows rows (None: 256 nlist, a seeded sample as in faiss);
+    the returned assignment is the nearest final centroid of EVERY row.  No host synchronisation, the same bits for the same seed."""
+    n, d = x.shape
+    nlist, iters = int(nlist), int(iters)
+    _check_l2_width("kmeans_l2", d)
+    if iters < 0:
+        raise ValueError(f"kmeans_l2: iters must be >= 0, got {iters}")
+    sample, init = kmeans_init(n, nlist, seed, train_rows)
+    xt = x if sample is None else x.index_select(0, sample.to(x.device)).contiguous()
+    cent = xt.index_select(0, init.to(x.device)).contiguous()
+    for _ in range(iters):
+        _, a = l2_knn_index(xt, cent, row_sqnorms(cent), 1)
+        sorted_a, order = torch.sort(a.reshape(-1), stable=True)
+        cent = segment_means(xt, order.to(torch.int32), cell_offsets(sorted_a, nlist), out=cent.clone())
+    _, assign = l2_knn_index(x, cent, row_sqnorms(cent), 1)
+    return cent, assign.reshape(-1)
+
+
 def bilinear_taps(nf, nc):
     """The sample positions csrc/patch_features.hip uses to resample nc positions to nf (F.interpolate's align_corners=False rule in
     integer arithmetic): per destination index i, num = max((2 i + 1) nc - nf, 0), a = num // (2 nf), b = min(a + 1, nc - 1) and the

@@ -20,7 +20,7 @@ from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
 from . import models
 from .density import position_channels
-from .models import PeraNet, PositionGaussianDetector, check_coreset, check_gallery, check_image_scores, check_metric
+from .models import PeraNet, PositionGaussianDetector, check_coreset, check_gallery, check_image_scores, check_index, check_metric
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -416,10 +416,18 @@ def _check_gallery(gallery, detector, metric, patch_localization, bank, coreset)
     return int(gallery)
 
 
-def _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery=None):
+def _check_index(index, nlist, nprobe, index_options, detector, metric, gallery):
+    """The index option of the kNN detector (models.check_index; PatchCore's approximate search): 'ivf' = an inverted file over the
+    bank rows, Euclidean, without a gallery; either level, localization, dense_features and bank, with or without a coreset."""
+    if index != 'flat' and detector != 'knn':
+        raise ValueError(f"index={index!r} applies to detector='knn' only, got detector={detector!r}")
+    return check_index(index, nlist, nprobe, index_options, metric, gallery)
+
+
+def _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery=None, index='flat'):
     """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
     scores and their nearest bank rows, which the image level and the Gaussian do not have."""
-    check_image_scores(image_scores, neighbours, gallery)
+    check_image_scores(image_scores, neighbours, gallery, index)
     if image_scores is not None and not patch_localization:
         raise ValueError("image_scores needs patch_localization=True: the image level scores images already")
     if image_scores is not None and detector == 'gde':
@@ -494,7 +502,7 @@ def _pyramid_columns(detector, det_kw):
 
 
 def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options,
-                   gallery=None, dense_features='local'):
+                   gallery=None, dense_features='local', index='flat', nlist=None, nprobe=8, index_options=None):
     """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
     _check_detector(detector)
     _check_metric(metric, detector)
@@ -503,7 +511,8 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
     _check_bank(bank, mvtec_inference)
     _check_coreset(coreset, detector)
     _check_gallery(gallery, detector, metric, patch_localization, bank, coreset)
-    _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery)
+    _check_index(index, nlist, nprobe, index_options, detector, metric, gallery)
+    _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery, index)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
     if dense_features == 'pyramid' and detector == 'padim':
         det_kw.update(preselected=True, width=PYRAMID_WIDTH)     # the model writes the chosen columns only (_pyramid_columns)
@@ -514,6 +523,8 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
         det_kw["metric"] = metric
     if gallery is not None:
         det_kw["gallery"] = gallery
+    if index != 'flat':
+        det_kw.update(index=index, nlist=nlist, nprobe=nprobe, index_options=index_options)
     return models.DETECTORS[detector], det_kw
 
 
@@ -717,7 +728,8 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
               patch_localization: bool = False, detector: str = 'knn', bank: str = 'reference',
               coreset=None, image_scores: str = None, neighbours: int = 9,
               localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine',
-              dense_features: str = 'local', gallery: int = None) -> ModelOutputsContainer:
+              dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
+              index_options: dict = None, gallery: int = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -747,9 +759,14 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     PaDiM's and SPADE's embedding: layer1, layer2 and layer3 as they are, the coarser maps replicated to layer1's grid, 448 columns
     (PeraNet.enable_dense_mode(features='pyramid'): 64 x 64 maps for 256 x 256 images).  With detector='padim' the model writes only
     the detector's `channels` columns (density.position_channels(448, channels, seed), the same draw on every rank) and the detector
-    reads them as they are (PositionGaussianDetector(preselected=True)); every other detector gets all 448."""
+    reads them as they are (PositionGaussianDetector(preselected=True)); every other detector gets all 448.
+    `index`: 'flat' (default) = the exact search; 'ivf' = an inverted file over the bank rows (AnomalyDetector(index='ivf'); PatchCore's
+    approximate search): `nlist` k-means cells (None: ceil(sqrt(R)) clamped to 1..4096), every patch meets the rows of its `nprobe`
+    nearest cells only -- approximate for nprobe < nlist, the scores never below the exact ones; `index_options`: {'iters', 'seed',
+    'train_rows'} of the k-means.  Needs detector='knn', metric='euclidean' and gallery=None; either level, localization,
+    dense_features and bank; with `coreset` the index is built over the rows the coreset kept; image_scores 'max' only."""
     cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
-                                 neighbours, detector_options, gallery, dense_features)
+                                 neighbours, detector_options, gallery, dense_features, index, nlist, nprobe, index_options)
     del TIMELINE[:]
     print('>>> initializing inference')
     plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
@@ -873,19 +890,20 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           metrics=('auroc', 'aupro', 'iou'), trainer_kwargs=None, tables_output: str = None, train: bool = True,
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
-          upsample_sigma: float = 4.0, dense_features: str = 'local', gallery: int = None):
+          upsample_sigma: float = 4.0, dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
+          index_options: dict = None, gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization`, `detector_options`, `metric`, `gallery` and `dense_features` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe` and `index_options` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
     `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps)."""
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
-                   gallery, dense_features)
+                   gallery, dense_features, index, nlist, nprobe, index_options)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}
@@ -900,6 +918,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw["gallery"] = gallery
     if dense_features != 'local':
         score_kw["dense_features"] = dense_features
+    if index != 'flat':
+        score_kw.update(index=index, nlist=nlist, nprobe=nprobe, index_options=index_options)
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
