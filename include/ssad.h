@@ -565,6 +565,24 @@ int ssad_l2_knn_index_split(const float* x, const float* bank, const float* bank
 int ssad_l2_from_dots(const float* sim, const float* qsq, const float* bsq, float* out, int64_t Q, int R, void* stream);
 int ssad_knn_reweight_l2(const float* xs, const float* bank, const int* mstar, const int* nbr, const float* smax, float* out, int64_t Q,
                          int D, int R, int bp, void* stream);
+/* Half-precision operands for the flat Euclidean search (csrc/knn_l2_half.hip; faiss' GpuIndexFlat useFloat16): the distance of the
+ * rows ROUNDED to fp16, d = sqrt(max(|h(q)|^2 + |h(b)|^2 - 2 <h(q), h(b)>, 0)), the dot product on v_mfma_f32_32x32x16_f16 (fp16
+ * products, fp32 accumulation).  h: fp32 -> fp16, round to nearest even, saturating at +-65504, results of magnitude below 2^-14
+ * flushed to signed zero: no half holds inf, NaN or a subnormal.
+ * ssad_rows_to_half: xh[n][j] = h(x[n][j]) (xh: [N][D] halves) and sq[n] = sum_j xh[n][j]^2 in fp32 in ssad_row_sqnorms' order, one
+ *   pass: equal rounded rows give equal norm bits wherever they stand.  D % 32 == 0, D <= 65536.
+ * ssad_l2h_knn_fused / _split / _index / _index_split: the four ssad_l2_knn entry points on rounded rows -- xh [N][D] and bankh [R][D]
+ *   halves (16-byte aligned), x_sq [N] and bank_sq [R] their norms from ssad_rows_to_half; out, dist, idx, part, S, k and the bit
+ *   claims (the same bits for every S and on every call; the index form's distances average to out's bits) as there. */
+int ssad_rows_to_half(const float* x, void* xh, float* sq, int64_t N, int D, void* stream);
+int ssad_l2h_knn_fused(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* out, int64_t N, int D, int R,
+                       int k, void* stream);
+int ssad_l2h_knn_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* part, float* out, int64_t N,
+                       int D, int R, int k, int S, void* stream);
+int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* dist, int* idx, int64_t N,
+                       int D, int R, int k, void* stream);
+int ssad_l2h_knn_index_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
+                             int* idx, int64_t N, int D, int R, int k, int S, void* stream);
 /* SPADE's image-conditioned gallery for the Euclidean kNN (csrc/knn_gallery.hip; Cohen & Hoshen 2020): a query image is scored against
  * the rows of K bank images only.  Queries x [Q P][D] and bank [T P][D] hold P rows per image, image after image.
  * ssad_group_means: out[g][c] = mean_i x[g P + i][c], the image descriptor: summed in fp64 in row order 0 .. P - 1, rounded once to

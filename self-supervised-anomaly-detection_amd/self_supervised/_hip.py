@@ -59,6 +59,12 @@ SIGNATURES = {
     "ssad_l2_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2_from_dots": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_fp],
     "ssad_knn_reweight_l2": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    # half-precision operands for the flat Euclidean search (csrc/knn_l2_half.hip)
+    "ssad_rows_to_half": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_fp],
+    "ssad_l2h_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2h_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2h_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2h_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_group_means": [_c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
     "ssad_l2_direct": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
     "ssad_l2_knn_gallery": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_fp],

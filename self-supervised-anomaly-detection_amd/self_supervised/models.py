@@ -521,6 +521,30 @@ def check_gallery(gallery, metric='euclidean', coreset=None):
     return int(gallery)
 
 
+BANK_DTYPES = ('float32', 'float16')
+
+
+def check_bank_dtype(bank_dtype, metric='euclidean', index='flat', gallery=None, image_scores=None):
+    """ValueError unless `bank_dtype` is 'float32' (default: the bank rows as they are) or 'float16' (the flat Euclidean search with
+    half-precision operands, csrc/knn_l2_half.hip: faiss' useFloat16) with metric='euclidean' (the half kernel is Euclidean),
+    index='flat' and gallery=None (it is the whole-bank search) and `image_scores` None or 'max' ('reweighted' takes direct fp32
+    differences to bank rows, which a half bank no longer has)."""
+    if bank_dtype not in BANK_DTYPES:
+        raise ValueError(f"bank_dtype must be one of {BANK_DTYPES}, got {bank_dtype!r}")
+    if bank_dtype == 'float32':
+        return bank_dtype
+    if metric != 'euclidean':
+        raise ValueError(f"bank_dtype='float16' needs metric='euclidean' (the half-precision kernel is Euclidean), got metric={metric!r}")
+    if index != 'flat':
+        raise ValueError(f"bank_dtype='float16' needs index='flat' (it is the exact search over the whole bank), got index={index!r}")
+    if gallery is not None:
+        raise ValueError("bank_dtype='float16' needs gallery=None: the gallery kernel reads fp32 bank rows")
+    if image_scores not in (None, 'max'):
+        raise ValueError(f"bank_dtype='float16' takes image_scores None or 'max', got {image_scores!r}: 'reweighted' takes direct fp32 "
+                         "differences to bank rows, which the half bank no longer holds")
+    return bank_dtype
+
+
 INDEXES = ('flat', 'ivf')
 IVF_OPTIONS = ('iters', 'seed', 'train_rows')
 IVF_MAX_NLIST = 4096
@@ -603,11 +627,19 @@ class AnomalyDetector(Detector):
     the search is APPROXIMATE for nprobe < nlist -- a score is never smaller than the exact one -- and exact, bit for bit, for
     nprobe = nlist.  The threshold goes through the same search.  ``kneighbors`` returns the caller's rows (before the sort); a
     slot the probed cells cannot fill is (+inf, -1).  Needs metric='euclidean' and gallery=None; works at both levels and with a
-    coreset.  image_scores takes 'max' only: 'reweighted' and 'retrieval' raise."""
+    coreset.  image_scores takes 'max' only: 'reweighted' and 'retrieval' raise.
+
+    `bank_dtype` (opt-in; faiss' useFloat16 on its GPU flat index): 'float32' (default) = the bank rows as they are; 'float16' = THE
+    OPERANDS ARE ROUNDED TO fp16: after the coreset selection (which runs on the fp32 rows) `bank` keeps the rows rounded by h
+    (ops.rows_to_half: round to nearest even, saturating at +-65504, subnormal results flushed) as torch.float16 and `bank_sq` the
+    squared norms of the rounded rows; the fp32 rows are dropped.  Queries are rounded the same way per call and every distance is
+    that BETWEEN THE ROUNDED ROWS, on the fp16 matrix cores with fp32 accumulation (ops.l2h_knn_fused / l2h_knn_index) -- it differs
+    from the fp32 search's by the rounding of the operands (relative 2^-11 per element).  Needs metric='euclidean', index='flat' and
+    gallery=None; works at both levels and with a coreset; image_scores takes 'max' only."""
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
                  coreset_dim: int = 128, metric: str = 'cosine', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-                 index_options: dict = None, gallery: int = None) -> None:
+                 index_options: dict = None, bank_dtype: str = 'float32', gallery: int = None) -> None:
         super().__init__(patch_level, batch, num_patches)
         self.k = 3
         self.bank = None
@@ -628,6 +660,8 @@ class AnomalyDetector(Detector):
         self.nprobe = int(nprobe)
         self.index_options = dict(index_options or {})
         self.ivf = None                 # index='ivf' after fit: perm, offsets, centroids, cent_sq, nlist, nprobe (bank: sorted by cell)
+        self.bank_dtype = check_bank_dtype(bank_dtype, self.metric, self.index, self.gallery)
+        self._rows32 = None             # bank_dtype='float16', inside fit with a coreset: the fp32 rows the selection runs on
 
     def _whole_images(self, what, rows: int) -> int:
         if rows < 1 or rows % self.patches:
@@ -659,7 +693,7 @@ class AnomalyDetector(Detector):
             r = int(self.bank.shape[0])
             m = coreset_size(self.coreset, r)
             if m < r:
-                sel, rad = coreset_select(self.bank, m, self.coreset_dim)
+                sel, rad = coreset_select(self.bank if self._rows32 is None else self._rows32, m, self.coreset_dim)
                 self.bank = self.bank.index_select(0, sel).contiguous()
                 if self.bank_sq is not None:
                     self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
@@ -697,8 +731,23 @@ class AnomalyDetector(Detector):
         if d % 32:
             raise ValueError(f"{what}: metric='euclidean' needs an embedding width that is a multiple of 32, got {d}")
 
+    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
+        if self.bank_dtype != 'float16' or self.coreset is None:
+            return super().fit(embeddings, split, groups)
+        self._rows32 = True             # fit_bank keeps the fp32 rows for the coreset selection of _after_bank
+        try:
+            super().fit(embeddings, split, groups)
+        finally:
+            self._rows32 = None
+
     def fit_bank(self, bank: Tensor) -> None:
         self.ivf = None                 # the rows as given: an index is built by fit (_after_bank) or arrives with load_state
+        if self.bank_dtype == 'float16':
+            self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
+            rows = self._dev(bank)
+            self.bank, self.bank_sq = ops.rows_to_half(rows)
+            self._rows32 = rows if self._rows32 is not None else None
+            return
         if self.metric == 'euclidean':
             self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
             if self.gallery is not None:
@@ -715,6 +764,8 @@ class AnomalyDetector(Detector):
         gallery the state names it (`gallery`: K); `bank_desc` is recomputed like `bank_sq`.  With index='ivf' `bank` is the bank
         sorted by cell and the state also carries `perm`, `offsets`, `centroids`, `nlist` and `nprobe`."""
         state = {"metric": self.metric, "bank": self.bank.cpu()}
+        if self.bank_dtype != 'float32':
+            state["bank_dtype"] = self.bank_dtype       # `bank` holds the rounded rows as torch.float16
         if self.gallery is not None:
             state["gallery"] = self.gallery
         if self.index == 'ivf':
@@ -729,6 +780,14 @@ class AnomalyDetector(Detector):
             raise ValueError(f"load_state: the bank was fitted with metric={state['metric']!r}, this detector has {self.metric!r}")
         if state.get("gallery") != self.gallery:
             raise ValueError(f"load_state: the bank was fitted with gallery={state.get('gallery')!r}, this detector has {self.gallery!r}")
+        if state.get("bank_dtype", 'float32') != self.bank_dtype:
+            raise ValueError(f"load_state: the bank was fitted with bank_dtype={state.get('bank_dtype', 'float32')!r}, this detector has "
+                             f"{self.bank_dtype!r}")
+        if self.bank_dtype == 'float16':
+            # the halves are fixed points of h, so rounding their fp32 values again returns them and the norms in the fit's order
+            self.bank, self.bank_sq = ops.rows_to_half(self._dev(state["bank"]))
+            self.ivf = None
+            return
         if self.gallery is not None:
             self._whole_images("load_state", int(state["bank"].shape[0]))
         self.bank = self._dev(state["bank"])
@@ -757,6 +816,9 @@ class AnomalyDetector(Detector):
         return order[:, :kq].to(torch.int32).contiguous(), vals[:, :kq].contiguous()
 
     def _scores(self, x):
+        if self.bank_dtype == 'float16':
+            self._check_width("predict", x.shape[1])
+            return ops.l2h_knn_fused(x, self.bank, self.bank_sq, self.k)
         if self.gallery is not None:
             self._check_width("predict", x.shape[1])
             gallery, _ = self.retrieve(x)
@@ -792,7 +854,9 @@ class AnomalyDetector(Detector):
         x = self._dev(x)
         if x.shape[1] % 32:
             raise ValueError(f"kneighbors: the index kernel needs an embedding width that is a multiple of 32, got {x.shape[1]}")
-        if self.gallery is not None:
+        if self.bank_dtype == 'float16':
+            dist, idx = ops.l2h_knn_index(x, self.bank, self.bank_sq, self.k if k is None else k)
+        elif self.gallery is not None:
             gallery, _ = self.retrieve(x)
             dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, self.k if k is None else k)
         elif self.index == 'ivf':
@@ -817,6 +881,7 @@ class AnomalyDetector(Detector):
 
     def _check_image_scores(self, mode, neighbours) -> None:
         check_image_scores(mode, neighbours, self.gallery, self.index)
+        check_bank_dtype(self.bank_dtype, self.metric, self.index, self.gallery, mode)
         if not self.patch_level or not self.dim:
             raise ValueError("image_scores needs a patch-level detector (patch_level=True with num_patches)")
         if self.bank is None:

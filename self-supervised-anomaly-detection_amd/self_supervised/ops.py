@@ -914,6 +914,78 @@ def l2_knn_index(x, bank, bank_sq, k=3, splits=None):
     return dist, idx
 
 
+def rows_to_half(x):
+    """x [N][D] fp32 -> (xh [N][D] float16, sq [N] float32): every element rounded by h (round to nearest even, saturating at +-65504,
+    results below 2^-14 flushed to signed zero) and the squared norms of the ROUNDED rows in row_sqnorms' order, one pass
+    (csrc/knn_l2_half.hip ssad_rows_to_half)."""
+    n, d = x.shape
+    _check_l2_width("rows_to_half", d)
+    xh = torch.empty((n, d), device=x.device, dtype=torch.float16)
+    sq = _new((n,), x)
+    _run("rows_to_half", 2.0 * n * d, 6.0 * x.numel() + 4.0 * n,
+         lambda: _hip.lib().ssad_rows_to_half(_hip.ptr(x), _hip.hptr(xh), _hip.ptr(sq), n, d, _hip.stream()))
+    return xh, sq
+
+
+def _l2h_args(name, x, bank_h, bank_sq, k, splits):
+    n, d = x.shape
+    r = bank_h.shape[0]
+    k = int(k)
+    _check_l2_width(name, d)
+    if bank_h.dtype != torch.float16 or bank_h.shape[1] != d or bank_sq.shape[0] != r:
+        raise ValueError(f"{name}: the bank must be [R][{d}] float16 rows with their [R] squared norms (rows_to_half)")
+    if not 1 <= k <= 3:
+        raise ValueError(f"{name}: k must be 1, 2 or 3, got {k}")
+    if r < k:
+        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"{name}: splits must be >= 1, got {s}")
+    return n, d, r, k, s
+
+
+def l2h_knn_fused(x, bank_h, bank_sq, k=3, splits=None):
+    """l2_knn_fused with half-precision operands: x [N][D] fp32 queries (rounded here, rows_to_half), (bank_h, bank_sq) =
+    rows_to_half(bank) -> [N] mean of the k smallest distances BETWEEN THE ROUNDED ROWS, sqrt(max(|h(x)|^2 + |h(b)|^2 - 2 <h(x), h(b)>,
+    0)), on the fp16 matrix cores (csrc/knn_l2_half.hip ssad_l2h_knn_fused / _split).  `splits` as in l2_knn_fused; the same bits for
+    every S."""
+    n, d, r, k, s = _l2h_args("l2h_knn_fused", x, bank_h, bank_sq, k, splits)
+    xh, xsq = rows_to_half(x)
+    out = _new((n,), x)
+    if s == 1:
+        _run("l2h_knn_fused", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + 2 * n),
+             lambda: _hip.lib().ssad_l2h_knn_fused(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(out), n, d,
+                                                   r, k, _hip.stream()))
+        return out
+    part = _new((s, n, 3), x)
+    _run("l2h_knn_split", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + 2 * n + 6 * part.numel()),
+         lambda: _hip.lib().ssad_l2h_knn_split(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(part),
+                                               _hip.ptr(out), n, d, r, k, s, _hip.stream()))
+    return out
+
+
+def l2h_knn_index(x, bank_h, bank_sq, k=3, splits=None):
+    """l2_knn_index with half-precision operands (arguments as l2h_knn_fused): (dist [N][k] float32, idx [N][k] int32), the k smallest
+    (squared distance, bank row) pairs between the rounded rows, equal ones to the smaller row; dist holds the bits l2h_knn_fused
+    averages (csrc/knn_l2_half.hip ssad_l2h_knn_index / _split)."""
+    n, d, r, k, s = _l2h_args("l2h_knn_index", x, bank_h, bank_sq, k, splits)
+    xh, xsq = rows_to_half(x)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    i32 = torch.int32
+    if s == 1:
+        _run("l2h_knn_index", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + n + 2 * n * k),
+             lambda: _hip.lib().ssad_l2h_knn_index(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(dist),
+                                                   _hip.ptr(idx, dtype=i32), n, d, r, k, _hip.stream()))
+        return dist, idx
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64)       # (squared-distance bits << 32 | row) keys
+    _run("l2h_knn_index_split", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + n + 2 * n * k) + 16.0 * part.numel(),
+         lambda: _hip.lib().ssad_l2h_knn_index_split(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq),
+                                                     _hip.ptr(part, dtype=torch.int64), _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d,
+                                                     r, k, s, _hip.stream()))
+    return dist, idx
+
+
 def l2_from_dots(sim, qsq, bsq):
     """sim [Q][R] dot products, qsq [Q], bsq [R] squared norms -> [Q][R] SQUARED Euclidean distances max(qsq + bsq - 2 sim, 0)
     (csrc/knn_l2.hip ssad_l2_from_dots; the kNN kernels' expression)."""

@@ -20,7 +20,8 @@ from .constants import METRICS, EvaluationOutputContainer, ModelOutputsContainer
 from .datasets import MVTecDatamodule, PretextTaskDatamodule
 from . import models
 from .density import position_channels
-from .models import PeraNet, PositionGaussianDetector, check_coreset, check_gallery, check_image_scores, check_index, check_metric
+from .models import PeraNet, PositionGaussianDetector, check_bank_dtype, check_coreset, check_gallery, check_image_scores, check_index, \
+    check_metric
 from .trainer import MetricTracker, ModelCheckpoint, Trainer, barrier, broadcast_bank, gather_in_order, local_only, world_info
 
 
@@ -424,6 +425,14 @@ def _check_index(index, nlist, nprobe, index_options, detector, metric, gallery)
     return check_index(index, nlist, nprobe, index_options, metric, gallery)
 
 
+def _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores):
+    """The bank_dtype option of the kNN detector (models.check_bank_dtype; faiss' useFloat16): 'float16' = the flat Euclidean search
+    with operands rounded to fp16; either level, localization, dense_features and bank, with or without a coreset."""
+    if bank_dtype != 'float32' and bank_dtype in models.BANK_DTYPES and detector != 'knn':
+        raise ValueError(f"bank_dtype={bank_dtype!r} applies to detector='knn' only, got detector={detector!r}")
+    return check_bank_dtype(bank_dtype, metric, index, gallery, image_scores)
+
+
 def _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery=None, index='flat'):
     """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
     scores and their nearest bank rows, which the image level and the Gaussian do not have."""
@@ -502,7 +511,7 @@ def _pyramid_columns(detector, det_kw):
 
 
 def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options,
-                   gallery=None, dense_features='local', index='flat', nlist=None, nprobe=8, index_options=None):
+                   gallery=None, dense_features='local', index='flat', nlist=None, nprobe=8, index_options=None, bank_dtype='float32'):
     """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
     _check_detector(detector)
     _check_metric(metric, detector)
@@ -513,6 +522,7 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
     _check_gallery(gallery, detector, metric, patch_localization, bank, coreset)
     _check_index(index, nlist, nprobe, index_options, detector, metric, gallery)
     _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery, index)
+    _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
     if dense_features == 'pyramid' and detector == 'padim':
         det_kw.update(preselected=True, width=PYRAMID_WIDTH)     # the model writes the chosen columns only (_pyramid_columns)
@@ -525,6 +535,8 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
         det_kw["gallery"] = gallery
     if index != 'flat':
         det_kw.update(index=index, nlist=nlist, nprobe=nprobe, index_options=index_options)
+    if bank_dtype != 'float32':
+        det_kw["bank_dtype"] = bank_dtype
     return models.DETECTORS[detector], det_kw
 
 
@@ -729,7 +741,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
               coreset=None, image_scores: str = None, neighbours: int = 9,
               localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine',
               dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-              index_options: dict = None, gallery: int = None) -> ModelOutputsContainer:
+              index_options: dict = None, bank_dtype: str = 'float32', gallery: int = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -764,9 +776,14 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     approximate search): `nlist` k-means cells (None: ceil(sqrt(R)) clamped to 1..4096), every patch meets the rows of its `nprobe`
     nearest cells only -- approximate for nprobe < nlist, the scores never below the exact ones; `index_options`: {'iters', 'seed',
     'train_rows'} of the k-means.  Needs detector='knn', metric='euclidean' and gallery=None; either level, localization,
-    dense_features and bank; with `coreset` the index is built over the rows the coreset kept; image_scores 'max' only."""
+    dense_features and bank; with `coreset` the index is built over the rows the coreset kept; image_scores 'max' only.
+    `bank_dtype`: 'float32' (default) = the bank rows as they are; 'float16' = the flat Euclidean search with half-precision operands
+    (AnomalyDetector(bank_dtype='float16'); faiss' useFloat16): bank rows and queries ARE ROUNDED TO fp16, so the distances are those
+    between the rounded rows; the bank takes half the memory, on every rank and in the broadcast.  Needs detector='knn',
+    metric='euclidean', index='flat' and gallery=None; either level, localization, dense_features and bank, with or without a
+    coreset (selected on the fp32 rows); image_scores 'max' only."""
     cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
-                                 neighbours, detector_options, gallery, dense_features, index, nlist, nprobe, index_options)
+                                 neighbours, detector_options, gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype)
     del TIMELINE[:]
     print('>>> initializing inference')
     plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
@@ -891,19 +908,19 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
           upsample_sigma: float = 4.0, dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-          index_options: dict = None, gallery: int = None):
+          index_options: dict = None, bank_dtype: str = 'float32', gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe` and `index_options` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe`, `index_options` and `bank_dtype` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
     `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps)."""
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
-                   gallery, dense_features, index, nlist, nprobe, index_options)
+                   gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype)
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
     rows, image_rows = {}, {}
@@ -920,6 +937,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw["dense_features"] = dense_features
     if index != 'flat':
         score_kw.update(index=index, nlist=nlist, nprobe=nprobe, index_options=index_options)
+    if bank_dtype != 'float32':
+        score_kw["bank_dtype"] = bank_dtype
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
