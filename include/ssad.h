@@ -140,7 +140,7 @@ int ssad_gap_fwd(const float* in, float* out, int64_t N, int HW, int C, int out_
 
 /* ---- scoring ---- */
 /* Replaces sklearn NearestNeighbors(metric='cosine').kneighbors + torch.mean (models.py:352-370).
- * l2norm: out[i] = x[i] / ||x[i]||.  knn3: given sim[Nq][Nb] = qn . bn, writes mean of the 3 smallest
+ * l2norm: out[i] = x[i] / ||x[i]||, a row whose fp32 sum of squares is exactly 0 divided by 1 (sklearn's normalize).  knn3: given sim[Nq][Nb] = qn . bn, writes mean of the 3 smallest
  * clip(1 - sim, 0, 2) per row. */
 int ssad_l2_normalize_rows(const float* x, float* out, int64_t N, int D, void* stream);
 int ssad_cosine_knn_mean(const float* sim, float* out, int64_t Nq, int Nb, int k, void* stream);

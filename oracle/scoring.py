@@ -32,12 +32,18 @@ def cosine_knn_mean(bank, queries, k=3):
 
     sklearn: Xn = X/||X||, Yn = Y/||Y||; D = clip(1 - Xn @ Yn.T, 0, 2); k smallest per row,
     sorted ascending; the reference then averages the k distances (models.py:366-368).
+    A row whose fp32 sum of squares is exactly 0 is divided by 1 (sklearn.preprocessing.normalize):
+    it is at distance 1 from every row.
     Returns (mean (Nq,), dists (Nq,k), idx (Nq,k)).
     """
     b = np.asarray(bank, dtype=np.float32)
     q = np.asarray(queries, dtype=np.float32)
-    bn = b / np.sqrt(np.einsum("ij,ij->i", b, b))[:, None]
-    qn = q / np.sqrt(np.einsum("ij,ij->i", q, q))[:, None]
+
+    def unit(v):
+        ss = np.einsum("ij,ij->i", v, v)
+        return v / np.where(ss == 0, np.float32(1), np.sqrt(ss))[:, None]
+
+    bn, qn = unit(b), unit(q)
     d = 1.0 - qn @ bn.T
     np.clip(d, 0, 2, out=d)
     idx = np.argsort(d, axis=1, kind="stable")[:, :k]

@@ -32,7 +32,7 @@ __global__ void gde_row_norms_kernel(const float* __restrict__ x, float* __restr
     for (int k = lane; k < D; k += 64) s += p[k] * p[k];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) nrm[row] = sqrtf(s);
+    if (lane == 0) nrm[row] = s == 0.f ? 1.f : sqrtf(s);       // a zero sum divides by 1, as l2norm_rows_kernel does
 }
 
 // the fp32 row element the statistics are of: x itself, or l2norm_rows_kernel's x / ||x||
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(NT, 2) void mahalanobis_fused_kernel(MahaParams p) 
                 float t = s[u];
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-                if (lane == 0) nrm_s[base + 4 * u] = m0 + base + 4 * u < p.N ? sqrtf(t) : 1.f;
+                if (lane == 0) nrm_s[base + 4 * u] = (m0 + base + 4 * u < p.N && t != 0.f) ? sqrtf(t) : 1.f;   // a zero sum divides by 1
             }
         }
         __syncthreads();

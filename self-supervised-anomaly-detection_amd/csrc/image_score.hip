@@ -116,7 +116,7 @@ __global__ __launch_bounds__(NT) void knn_reweight_kernel(const float* __restric
     for (int k = lane; k < D; k += 64) ss += x[k] * x[k];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    const float nrm = sqrtf(ss);
+    const float nrm = ss == 0.f ? 1.f : sqrtf(ss);          // a zero sum divides by 1, as l2norm_rows_kernel does
     for (int j = wave; j <= bp; j += NT / 64) {             // j = bp: the nearest row itself (the numerator)
         const int row = j < bp ? nbr[(int64_t)blockIdx.x * bp + j] : mstar[blockIdx.x];
         float dot = 0.f;

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_fused_kernel(KnnParams p) {
             float t = s[u];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-            if (lane == 0) nrm_s[base + 4 * u] = sqrtf(t);
+            if (lane == 0) nrm_s[base + 4 * u] = t == 0.f ? 1.f : sqrtf(t);     // a zero sum divides by 1 (l2norm_rows_kernel)
         }
     }
     __syncthreads();
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_split_kernel(KnnSplitParams 
             float t = s[u];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-            if (lane == 0) nrm_s[base + 4 * u] = m0 + base + 4 * u < p.N ? sqrtf(t) : 1.f;
+            if (lane == 0) nrm_s[base + 4 * u] = (m0 + base + 4 * u < p.N && t != 0.f) ? sqrtf(t) : 1.f;   // a zero sum divides by 1
         }
     }
     __syncthreads();
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_index_kernel(KnnIndexParams 
             float t = s[u];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-            if (lane == 0) nrm_s[base + 4 * u] = m0 + base + 4 * u < p.N ? sqrtf(t) : 1.f;
+            if (lane == 0) nrm_s[base + 4 * u] = (m0 + base + 4 * u < p.N && t != 0.f) ? sqrtf(t) : 1.f;   // a zero sum divides by 1
         }
     }
     __syncthreads();

@@ -85,7 +85,8 @@ __global__ __launch_bounds__(256) void gap_wide_kernel(const T* __restrict__ in,
     }
 }
 
-// one wave per row
+// one wave per row.  A row whose fp32 sum of squares is exactly 0 (a zero row, or squares that all underflow) is divided by 1: the rule of
+// sklearn.preprocessing.normalize, which the cosine metric of the reference goes through -- such a row is at distance 1 from every row.
 __global__ void l2norm_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t N, int D) {
     int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= N) return;
@@ -95,7 +96,7 @@ __global__ void l2norm_rows_kernel(const float* __restrict__ x, float* __restric
     for (int k = lane; k < D; k += 64) s += p[k] * p[k];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    float nrm = sqrtf(s);
+    float nrm = s == 0.f ? 1.f : sqrtf(s);
     for (int k = lane; k < D; k += 64) out[row * D + k] = p[k] / nrm;
 }
 

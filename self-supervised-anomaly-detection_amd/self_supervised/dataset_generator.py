@@ -35,8 +35,26 @@ def _canny(gray, sigma, low, high):
     by 255 accordingly), Gaussian smoothing with zero ('constant') borders renormalised by the smoothed all-ones mask, Sobel
     derivatives, non-maximum suppression by bilinear interpolation of the magnitude along the gradient direction on the
     border-eroded mask, double threshold and hysteresis over 8-connected components."""
+    out = _canny_thinned(gray, sigma, low)
+    if out is None:
+        return np.zeros(gray.shape, bool)
+    high = high / 255.0
+    low_mask = out > 0
+    lab, n = ndimage.label(low_mask, structure=np.ones((3, 3), int))
+    if n == 0:
+        return low_mask
+    high_mask = low_mask & (out >= high)
+    sums = ndimage.sum_labels(high_mask, lab, np.arange(n + 1))
+    good = sums > 0
+    good[0] = False
+    return good[lab]
+
+
+def _canny_thinned(gray, sigma, low):
+    """The first half of _canny: the gradient magnitude after non-maximum suppression and the low threshold (0 elsewhere), the plane
+    hysteresis runs on; None for an image with a side below 3 (no interior pixel: no edges)."""
     img = gray.astype(np.float64) / 255.0
-    low, high = low / 255.0, high / 255.0
+    low = low / 255.0
     bleed = ndimage.gaussian_filter(np.ones_like(img), sigma, mode="constant", cval=0.0) + np.finfo(np.float64).eps
     sm = ndimage.gaussian_filter(img, sigma, mode="constant", cval=0.0) / bleed
     js = ndimage.sobel(sm, axis=1)
@@ -45,7 +63,7 @@ def _canny(gray, sigma, low, high):
     h, w = mag.shape
     out = np.zeros_like(mag)
     if h < 3 or w < 3:
-        return np.zeros(mag.shape, bool)
+        return None
     c = (slice(1, -1), slice(1, -1))
 
     def sh(dx, dy):                                  # magnitude at (row + dx, col + dy) for the interior pixels
@@ -71,15 +89,7 @@ def _canny(gray, sigma, low, high):
     test(b, w_ij, sh(0, 1), sh(-1, 1), sh(0, -1), sh(1, -1))
     test(c2 & ~b, w_ji, sh(-1, 0), sh(-1, 1), sh(1, 0), sh(1, -1))
     out[c] = np.where(keep & ok, m, 0.0)
-    low_mask = out > 0
-    lab, n = ndimage.label(low_mask, structure=np.ones((3, 3), int))
-    if n == 0:
-        return low_mask
-    high_mask = low_mask & (out >= high)
-    sums = ndimage.sum_labels(high_mask, lab, np.arange(n + 1))
-    good = sums > 0
-    good[0] = False
-    return good[lab]
+    return out
 
 
 def obj_mask(image: Image.Image) -> Image.Image:

@@ -1785,10 +1785,11 @@ def pro_weights(labels, offsets, area):
 def gradcam_map(act, alpha):
     """act NHWC [B][U][V][C], alpha [B][C] (may be a column slice of a wider matrix) -> [B][1][U][V] weighted sums."""
     b, u, v, c = act.shape
-    assert alpha.shape == (b, c) and alpha.stride(1) == 1
+    assert alpha.shape == (b, c) and alpha.stride(1) == 1 and (b == 1 or alpha.stride(0) >= c)
+    assert alpha.is_cuda and alpha.dtype == torch.float32         # rows may be strided (a slice): _hip.ptr would refuse them
     out = _new((b, 1, u, v), act)
     _run("gradcam_map", 2.0 * act.numel(), 4.0 * act.numel(),
-         lambda: _hip.lib().ssad_gradcam_map(_hip.ptr(act), _hip.ptr(alpha), _hip.ptr(out), b, u * v, c, alpha.stride(0),
+         lambda: _hip.lib().ssad_gradcam_map(_hip.ptr(act), alpha.data_ptr(), _hip.ptr(out), b, u * v, c, max(alpha.stride(0), c),
                                              _hip.stream()))
     return out
 
