@@ -666,11 +666,12 @@ int ssad_coreset_greedy(const float* p, int64_t R, int d, int m, int64_t start, 
 /* Gaussian density estimator (GDE) scorer of CutPaste (csrc/gde.hip; the reference has no such scorer).
  * ssad_gaussian_fit_stats: of the N rows of x [N][D] (each first L2-normalised bit-identically to ssad_l2_normalize_rows when
  * `normalize`), in fp64: mean[D], scatter[D][D] = sum_i (x_i - mean)(x_i - mean)^T and m4[0] = sum_i ||x_i - mean||^4 (the sufficient
- * statistics of sklearn's Ledoit-Wolf shrinkage).  Fixed-order reductions: the same bits on every call.  N >= 1, D % 32 == 0.
+ * statistics of sklearn's Ledoit-Wolf shrinkage).  Fixed-order reductions: the same bits on every call.  N >= 1, D % 32 == 0,
+ * 32 <= D <= 4096.
  * ssad_mahalanobis_fused: out[i] = ||W (x_i - mu)||_2 in one kernel on the fp32 matrix cores, mu = mu_hi + mu_lo (a float pair:
  * (x - mu_hi) - mu_lo), W [D][D] the lower-triangular inverse Cholesky factor of the shrunk covariance (its upper triangle is not
- * read); x_i optionally L2-normalised as above.  No split across workgroups: a row's score does not depend on N or on its position.
- * D % 32 == 0, 32 <= D <= 1024. */
+ * read: it may hold anything, NaN included); x_i optionally L2-normalised as above.  No split across workgroups: a row's score does
+ * not depend on N or on its position.  D % 32 == 0, 32 <= D <= 1024. */
 int ssad_gaussian_fit_stats(const float* x, int64_t N, int D, int normalize, double* mean, double* scatter, double* m4, void* stream);
 int ssad_mahalanobis_fused(const float* x, const float* mu_hi, const float* mu_lo, const float* w, float* out, int64_t N, int D,
                            int normalize, void* stream);

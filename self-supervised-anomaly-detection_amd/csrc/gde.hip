@@ -229,7 +229,9 @@ __global__ __launch_bounds__(NT, 2) void mahalanobis_fused_kernel(MahaParams p) 
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
         f32x4 rq[4], rb[4], mh, ml;
+        int kc = 0;                             // first column of the chunk the registers hold
         auto load = [&](int ks) {
+            kc = ks * BK + sc * 4;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xblk + ks * BK), 0, (int)OOB, SRD3);
             const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(wblk + ks * BK), 0, (int)OOB, SRD3);
 #pragma unroll
@@ -250,7 +252,11 @@ __global__ __launch_bounds__(NT, 2) void mahalanobis_fused_kernel(MahaParams p) 
                     if constexpr (NORM) v = v / nrm[i];                   // l2norm_rows_kernel's expression
                     c[k] = (v - mh[k]) - ml[k];                           // exact first difference near the mean (Sterbenz)
                 }
-                *(f32x4*)(st + (sr + 32 * i) * LDK + sc * 4) = rb[i];                   // W rows: the tile's M side
+                // W rows, the tile's M side: whatever sits above the diagonal is replaced by the zero it stands for
+                f32x4 wv;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) wv[k] = kc + k <= n0 + sr + 32 * i ? rb[i][k] : 0.f;
+                *(f32x4*)(st + (sr + 32 * i) * LDK + sc * 4) = wv;
                 *(f32x4*)(st + BB * LDK + (sr + 32 * i) * LDK + sc * 4) = c;            // centred queries: its N side
             }
         };
@@ -373,7 +379,8 @@ extern "C" int ssad_gaussian_fit_stats(const float* x, int64_t N, int D, int nor
     return rc;
 }
 
-// out[i] = ||W (x_i - mu)||_2, mu = mu_hi + mu_lo, W [D][D] lower triangular (its upper triangle is not read); x_i first
+// out[i] = ||W (x_i - mu)||_2, mu = mu_hi + mu_lo, W [D][D] lower triangular (its upper triangle is not read: what the tile loads of
+// it is replaced by zeros while staging, so it may hold anything, NaN included); x_i first
 // L2-normalised as ssad_l2_normalize_rows does when `normalize`.  32 <= D <= 1024, D % 32 == 0.  One workgroup scores 128 rows over
 // all of W: no split over K or W rows across workgroups, so a row's score is the same bits whatever N and wherever it sits.
 extern "C" int ssad_mahalanobis_fused(const float* x, const float* mu_hi, const float* mu_lo, const float* w, float* out, int64_t N,

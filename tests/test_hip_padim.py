@@ -94,7 +94,7 @@ def _score(rows, sel, dev, n, P):
 
 
 SCORE_SHAPES = [(1, 3, 64, 32), (127, 3, 64, 32), (128, 3, 64, 32), (129, 3, 64, 32), (40, 7, 384, 96), (40, 2, 384, 160),
-                (9, 144, 384, 96)]
+                (9, 144, 384, 96), (129, 2, 256, 128), (40, 2, 256, 256)]          # the last two: d = D = exactly one / two W tiles
 
 
 @pytest.mark.parametrize("shape", SCORE_SHAPES, ids=["x".join(map(str, s)) for s in SCORE_SHAPES])
