@@ -731,6 +731,27 @@ int64_t ssad_best_f1_workspace(int64_t n);
 int ssad_best_f1_threshold(const float* scores, const uint8_t* targets, int64_t n, void* workspace, int64_t workspace_bytes, float* out,
                            void* stream);
 int ssad_confusion_counts(const float* scores, const uint8_t* targets, int64_t n, float threshold, int64_t* out, void* stream);
+/* Average precision and the precision-recall curve of device-resident scores.  The reference has no AP (its Evaluator stops at
+ * AUROC / F1 / AUPRO / IoU); this replaces what a user would otherwise call on the host, sklearn.metrics.average_precision_score /
+ * precision_recall_curve.  Same radix sort as ssad_auroc, descending, the target as payload; scores fp32 [n], targets uint8 [n],
+ * non-zero = positive.  A threshold is a distinct score value (-0.0 and +0.0 are one value; NaN scores are not defined).  For the
+ * j-th distinct value in descending order, TP_j = positives with a score >= it, N_j = elements with a score >= it, P = TP_m:
+ *   AP = sum_j (TP_j - TP_{j-1}) / P * TP_j / N_j   (TP_0 = 0; sklearn's step-wise sum, no trapezoid; P = 0 gives AP = 0.0, the
+ *   value of sklearn's arithmetic with its "recall is set to one" convention).
+ * ssad_average_precision: out[0] = AP, out[1] = P, out[2] = m, the number of distinct scores.  Exact integer counts; every term is
+ *   formed in fp64 and the terms are summed per workgroup and then over the workgroups in an order fixed by n: no floating-point
+ *   atomics, the same bits on every call and for every order of the input.
+ * ssad_pr_curve: one point per distinct score in DESCENDING threshold order: precision = TP_j / N_j and recall = TP_j / P (1.0
+ *   when P = 0) fp64, thresholds fp32 (a run of zeros reports -0.0 when it holds one); their number goes to count[0] (device
+ *   memory; the arrays need room for n entries).  The caller appends sklearn's end point (precision 1, recall 0) and reverses.
+ * The workspace holds ssad_*_workspace(n) bytes (-1 for n <= 0 or n >= 2^31 - 1) and is aligned to 8 bytes.  A null pointer, n <= 0,
+ * a workspace too small or misaligned returns 2 with ssad_last_error() set, before anything is written. */
+int64_t ssad_average_precision_workspace(int64_t n);
+int ssad_average_precision(const float* scores, const uint8_t* targets, int64_t n, void* workspace, int64_t workspace_bytes,
+                           double* out, void* stream);
+int64_t ssad_pr_curve_workspace(int64_t n);
+int ssad_pr_curve(const float* scores, const uint8_t* targets, int64_t n, void* workspace, int64_t workspace_bytes,
+                  double* precision, double* recall, float* thresholds, int64_t* count, void* stream);
 
 /* transforms.ToTensor() on a uint8 HWC batch: -> [B][3][H][W] fp32 in [0,1] (the Dataset's third output). */
 int ssad_u8hwc_to_f32chw(const uint8_t* img, float* out, int B, int H, int W, void* stream);

@@ -505,3 +505,166 @@ extern "C" int ssad_confusion_counts(const float* scores, const uint8_t* targets
     SSAD_CHECK_LAUNCH();
     return 0;
 }
+
+// =============================================================================================
+// Average precision and the precision-recall curve (sklearn.metrics.average_precision_score / precision_recall_curve; the reference has
+// no AP: pixel AP is the figure DRAEM and anomalib report beside AUROC).  Same descending radix sort with the label as payload; then
+//   tps[i]  = inclusive int64 count of positives (exact),
+//   last[i] = index of the last run end at or before i (a running maximum over "i if i closes a run of equal scores, else -1"),
+// so that a run end i reads TP_j = tps[i], N_j = i + 1 and TP_{j-1} = tps[last[i - 1]] with two loads, whatever the run lengths.
+//   AP = sum_j (TP_j - TP_{j-1}) * (TP_j / N_j) / P
+// Every term is three correctly rounded fp64 operations on exact integers.  Workgroup b sums the terms of tile b (a thread its 16
+// positions in index order, then a fixed LDS tree), one workgroup sums the partials (thread t takes b = t, t + 256, ... in order, the
+// same tree): the order depends on n alone, there is no floating-point atomic, and the bits repeat from call to call.
+// =============================================================================================
+namespace {
+
+// tps[i] = 1 on a positive; mark[i] on the last element of a run of equal scores: its index (as_index; -1 elsewhere) or 1 (0 elsewhere)
+__global__ void ap_mark_kernel(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab, int64_t n, int as_index,
+                               int64_t* __restrict__ tps, int64_t* __restrict__ mark) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    tps[i] = lab[i] ? 1 : 0;
+    const bool end = i == n - 1 || score_of_desc(keys[i]) != score_of_desc(keys[i + 1]);
+    mark[i] = as_index ? (end ? i : -1) : (end ? 1 : 0);
+}
+
+__device__ __forceinline__ void ap_tree(double* a, double* b) {        // sums of a[0..256) and b[0..256) into a[0], b[0]: a fixed tree
+    __syncthreads();
+    for (int o = SORT_T / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { a[threadIdx.x] += a[threadIdx.x + o]; b[threadIdx.x] += b[threadIdx.x + o]; }
+        __syncthreads();
+    }
+}
+
+// partial[2 b] = the terms of tile b, partial[2 b + 1] = its number of run ends (at most 4096: exact)
+__global__ __launch_bounds__(SORT_T) void ap_terms_kernel(const int64_t* __restrict__ tps, const int64_t* __restrict__ last, int64_t n,
+                                                          double* __restrict__ partial) {
+    __shared__ double st[SORT_T];
+    __shared__ double sc[SORT_T];
+    const double P = (double)tps[n - 1];
+    const int64_t base = (int64_t)blockIdx.x * SORT_TILE;
+    double acc = 0, cnt = 0;
+#pragma unroll 4
+    for (int r = 0; r < SORT_ITEMS; ++r) {
+        const int64_t i = base + r * SORT_T + threadIdx.x;
+        if (i >= n || last[i] != i) continue;
+        cnt += 1.0;
+        const int64_t prev = i ? last[i - 1] : -1;
+        const int64_t tp = tps[i];
+        const int64_t d = tp - (prev >= 0 ? tps[prev] : 0);
+        if (d) acc += (double)d * ((double)tp / (double)(i + 1)) / P;        // d > 0 implies P > 0; no positive at all: AP = 0
+    }
+    st[threadIdx.x] = acc;
+    sc[threadIdx.x] = cnt;
+    ap_tree(st, sc);
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = st[0]; partial[2 * blockIdx.x + 1] = sc[0]; }
+}
+
+__global__ __launch_bounds__(SORT_T) void ap_finish_kernel(const double* __restrict__ partial, int nblk, const int64_t* __restrict__ tps,
+                                                           int64_t n, double* __restrict__ out) {
+    __shared__ double st[SORT_T];
+    __shared__ double sc[SORT_T];
+    double acc = 0, cnt = 0;
+    for (int b = threadIdx.x; b < nblk; b += SORT_T) { acc += partial[2 * b]; cnt += partial[2 * b + 1]; }
+    st[threadIdx.x] = acc;
+    sc[threadIdx.x] = cnt;
+    ap_tree(st, sc);
+    if (threadIdx.x == 0) { out[0] = st[0]; out[1] = (double)tps[n - 1]; out[2] = sc[0]; }
+}
+
+// one point per run end, in descending score order; pos = inclusive scan of the run-end flags
+__global__ void pr_compact_kernel(const uint32_t* __restrict__ keys, const int64_t* __restrict__ tps, const int64_t* __restrict__ pos,
+                                  int64_t n, double* __restrict__ precision, double* __restrict__ recall, float* __restrict__ thresholds,
+                                  int64_t* __restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t before = i ? pos[i - 1] : 0;
+    if (pos[i] != before) {
+        const int64_t tp = tps[i], P = tps[n - 1];
+        precision[before] = (double)tp / (double)(i + 1);
+        recall[before] = P ? (double)tp / (double)P : 1.0;          // sklearn: no positive class, recall is set to one
+        thresholds[before] = score_of_desc(keys[i]);                // the run's last key: -0.0 when the run of zeros holds one
+    }
+    if (i == n - 1) count[0] = pos[i];
+}
+
+struct ApWs {
+    uint32_t *kA, *kB, *bh;
+    uint8_t *lA, *lB;
+    int64_t *tps, *mark, *totals;
+    double* partial;
+};
+
+ApWs ap_carve(void* workspace, int64_t n, int nblk) {
+    ApWs s;
+    char* w = (char*)workspace;
+    s.kA = (uint32_t*)w; w += align256(n * 4);
+    s.kB = (uint32_t*)w; w += align256(n * 4);
+    s.lA = (uint8_t*)w; w += align256(n);
+    s.lB = (uint8_t*)w; w += align256(n);
+    s.bh = (uint32_t*)w; w += align256((size_t)256 * nblk * 4);
+    s.tps = (int64_t*)w; w += align256(n * 8);
+    s.mark = (int64_t*)w; w += align256(n * 8);
+    s.totals = (int64_t*)w; w += align256((size_t)nblk * 8);
+    s.partial = (double*)w;                                         // ssad_average_precision only
+    return s;
+}
+
+// sorted keys + labels, tps scanned, mark scanned with Op
+template <class Op>
+void ap_sort_and_scan(const float* scores, const uint8_t* targets, int64_t n, int nblk, const ApWs& s, int as_index, hipStream_t st) {
+    const unsigned g = (unsigned)cdiv64(n, 256);
+    hipLaunchKernelGGL(to_keys_desc_kernel, dim3(g), dim3(256), 0, st, scores, s.kA, n);
+    radix_sort_pairs<uint8_t>(s.kA, s.kB, s.lA, s.lB, targets, n, nblk, s.bh, st);
+    hipLaunchKernelGGL(ap_mark_kernel, dim3(g), dim3(256), 0, st, s.kA, s.lA, n, as_index, s.tps, s.mark);
+    inclusive_scan<SumOp>(s.tps, n, s.totals, nblk, st);
+    inclusive_scan<Op>(s.mark, n, s.totals, nblk, st);
+}
+
+}  // namespace
+
+extern "C" int64_t ssad_pr_curve_workspace(int64_t n) {
+    if (n <= 0 || n >= (int64_t)2147483647) return -1;
+    const int64_t nblk = cdiv64(n, SORT_TILE);
+    return (int64_t)(2 * align256(n * 4) + 2 * align256(n) + align256(256 * nblk * 4) + 2 * align256(n * 8) + align256(nblk * 8));
+}
+
+extern "C" int64_t ssad_average_precision_workspace(int64_t n) {
+    if (n <= 0 || n >= (int64_t)2147483647) return -1;
+    return ssad_pr_curve_workspace(n) + (int64_t)align256(cdiv64(n, SORT_TILE) * 16);
+}
+
+// scores fp32 [n], targets uint8 [n] (non-zero = positive) -> out[0] = AP (0 without a positive), out[1] = P, out[2] = distinct scores
+extern "C" int ssad_average_precision(const float* scores, const uint8_t* targets, int64_t n, void* workspace, int64_t workspace_bytes,
+                                      double* out, void* stream) {
+    SSAD_CHECK_ARG(scores && targets && workspace && out && n > 0 && n < (int64_t)2147483647, "bad argument");
+    SSAD_CHECK_ARG(workspace_bytes >= ssad_average_precision_workspace(n), "workspace too small (ssad_average_precision_workspace)");
+    SSAD_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace not aligned to 8 bytes");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)cdiv64(n, SORT_TILE);
+    const ApWs s = ap_carve(workspace, n, nblk);
+    ap_sort_and_scan<MaxOp>(scores, targets, n, nblk, s, 1, st);
+    hipLaunchKernelGGL(ap_terms_kernel, dim3(nblk), dim3(SORT_T), 0, st, s.tps, s.mark, n, s.partial);
+    hipLaunchKernelGGL(ap_finish_kernel, dim3(1), dim3(SORT_T), 0, st, s.partial, nblk, s.tps, n, out);
+    SSAD_CHECK_LAUNCH();
+    return 0;
+}
+
+// -> precision fp64, recall fp64, thresholds fp32 [count]: one point per distinct score, descending thresholds; count[0] in device
+// memory.  The caller appends sklearn's end point (precision 1, recall 0) and reverses.
+extern "C" int ssad_pr_curve(const float* scores, const uint8_t* targets, int64_t n, void* workspace, int64_t workspace_bytes,
+                             double* precision, double* recall, float* thresholds, int64_t* count, void* stream) {
+    SSAD_CHECK_ARG(scores && targets && workspace && precision && recall && thresholds && count && n > 0 && n < (int64_t)2147483647,
+                   "bad argument");
+    SSAD_CHECK_ARG(workspace_bytes >= ssad_pr_curve_workspace(n), "workspace too small (ssad_pr_curve_workspace)");
+    SSAD_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace not aligned to 8 bytes");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)cdiv64(n, SORT_TILE);
+    const ApWs s = ap_carve(workspace, n, nblk);
+    ap_sort_and_scan<SumOp>(scores, targets, n, nblk, s, 0, st);
+    hipLaunchKernelGGL(pr_compact_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, s.kA, s.tps, s.mark, n, precision, recall,
+                       thresholds, count);
+    SSAD_CHECK_LAUNCH();
+    return 0;
+}

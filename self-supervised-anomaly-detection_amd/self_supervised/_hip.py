@@ -177,6 +177,10 @@ SIGNATURES = {
     "ssad_best_f1_workspace": [_c_l],
     "ssad_best_f1_threshold": [_c_fp, _c_fp, _c_l, _c_fp, _c_l, _c_fp, _c_fp],
     "ssad_confusion_counts": [_c_fp, _c_fp, _c_l, _c_f, _c_fp, _c_fp],
+    "ssad_average_precision_workspace": [_c_l],
+    "ssad_average_precision": [_c_fp, _c_fp, _c_l, _c_fp, _c_l, _c_fp, _c_fp],
+    "ssad_pr_curve_workspace": [_c_l],
+    "ssad_pr_curve": [_c_fp, _c_fp, _c_l, _c_fp, _c_l, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_aug_params_size": [],
     "ssad_cutpaste_augment": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_i, _c_i,
                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _c_fp],
@@ -253,7 +257,7 @@ SIGNATURES = {
     "ssad_stem_wgrad_h": [_c_fp, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp],
 }
 RESTYPES = {"ssad_conv3x3_c64_stats_rows": _c_l, "ssad_conv3x3_h_stats_rows": _c_l, "ssad_conv3x3_hw_stats_rows": _c_l, "ssad_conv3x3_hw_packed_size": _c_l, "ssad_colreduce_workspace": _c_l, "ssad_conv_stats_workspace": _c_l, "ssad_stem_wgrad_workspace": _c_l, "ssad_auroc_workspace": _c_l, "ssad_obj_mask_workspace": _c_l, "ssad_pro_curve_workspace": _c_l,
-            "ssad_best_f1_workspace": _c_l, "ssad_label_regions_workspace": _c_l, "ssad_region_filter_workspace": _c_l}
+            "ssad_best_f1_workspace": _c_l, "ssad_average_precision_workspace": _c_l, "ssad_pr_curve_workspace": _c_l,"ssad_label_regions_workspace": _c_l, "ssad_region_filter_workspace": _c_l}
 
 _lib = None
 

@@ -2,7 +2,9 @@
 reference does, F1 at a threshold, and the MVTec per-region-overlap (PRO) curve with its clipped trapezoid area.
 The host functions are the parity statement (pinned to the reference's own metrics.py by tests/golden/metrics.npz); the `*_gpu`
 functions below compute the same quantities for device-resident maps with the hand-written radix sort of csrc/auroc.hip
-(three argsorts of 83 x 65 536 scores cost ~9 s per category on the host -- more than training that category on this card)."""
+(three argsorts of 83 x 65 536 scores cost ~9 s per category on the host -- more than training that category on this card).
+Beyond the reference: average precision and the precision-recall curve as scikit-learn defines them (compute_average_precision,
+compute_pr_curve, average_precision_gpu, pr_curve_gpu)."""
 from bisect import bisect
 
 import numpy as np
@@ -200,6 +202,92 @@ def compute_iou_gpu(scores, targets, threshold) -> float:
     for inter, union in ((tn, tn + fp + fn), (tp, tp + fp + fn)):          # class "normal", class "anomalous"
         ious.append(inter / union if union else 0.0)
     return float(np.mean(ious))
+
+
+def _pr_counts(labels, scores):
+    """-> (thresholds, TP, N, P): one entry per distinct score in DESCENDING order, TP / N = positives / elements with a score at
+    least the threshold (exact int64), P = positives.  -0.0 and +0.0 are one value, reported as -0.0 when one is present (the
+    last of the run in descending key order, as csrc/auroc.hip reports it).  Positive = non-zero label."""
+    s = _np(scores).reshape(-1)
+    y = _np(labels).reshape(-1) != 0
+    if s.size == 0:
+        raise ValueError("average precision / precision-recall curve of no scores")
+    if s.size != y.size:
+        raise ValueError(f"{y.size} labels for {s.size} scores")
+    if np.isnan(s).any():
+        raise ValueError("NaN scores: average precision is not defined on them")
+    order = np.lexsort((np.signbit(s), -s.astype(np.float64)))          # descending; among zeros +0.0 first
+    s, y = s[order], y[order]
+    end = np.append(s[1:] != s[:-1], True)
+    tp = np.cumsum(y, dtype=np.int64)[end]
+    return s[end], tp, np.flatnonzero(end).astype(np.int64) + 1, int(tp[-1])
+
+
+def compute_average_precision(labels, scores) -> float:
+    """Average precision as sklearn.metrics.average_precision_score defines it (the reference has no AP; pixel AP is what DRAEM and
+    anomalib report beside AUROC): AP = sum_j (TP_j - TP_{j-1}) / P * TP_j / N_j over the distinct scores in descending order, a
+    step-wise sum, no trapezoid.  Without a positive label AP = 0.0: the value of sklearn's arithmetic with its "recall is set to
+    one" convention.  NaN scores and empty inputs raise ValueError."""
+    _, tp, n, P = _pr_counts(labels, scores)
+    if P == 0:
+        return 0.0
+    d = np.diff(tp, prepend=0).astype(np.float64)
+    return float(np.sum(d * (tp / n) / P))
+
+
+def compute_pr_curve(labels, scores):
+    """(precision, recall, thresholds) in sklearn.metrics.precision_recall_curve's layout: ascending thresholds, one per distinct
+    score, and the end point (precision 1, recall 0) appended to the first two.  Without a positive label recall is 1 everywhere."""
+    thr, tp, n, P = _pr_counts(labels, scores)
+    precision = tp / n
+    recall = tp / P if P else np.ones(tp.size)
+    return np.append(precision[::-1], 1.0), np.append(recall[::-1], 0.0), thr[::-1].copy()
+
+
+def _ap_inputs(labels, scores, who):
+    s = scores.detach().reshape(-1).float().contiguous() if torch.is_tensor(scores) else None
+    if s is None or not s.is_cuda:
+        raise RuntimeError(f"{who} needs GPU tensors; use compute_average_precision / compute_pr_curve on the host")
+    if s.numel() == 0:
+        raise ValueError(f"{who}: no scores")
+    if bool(torch.isnan(s).any()):
+        raise ValueError(f"{who}: NaN scores: average precision is not defined on them")
+    t = (torch.as_tensor(labels).detach().reshape(-1).to(s.device) != 0).to(torch.uint8).contiguous()
+    if t.numel() != s.numel():
+        raise ValueError(f"{who}: {t.numel()} labels for {s.numel()} scores")
+    return s, t
+
+
+def average_precision_gpu(labels, scores) -> float:
+    """compute_average_precision for device-resident scores (csrc/auroc.hip: descending radix sort with the label as payload, exact
+    int64 counts, the terms summed in fp64 in a fixed order).  Equal to the host value up to the summation order."""
+    from . import _hip
+    s, t = _ap_inputs(labels, scores, "average_precision_gpu")
+    n = s.numel()
+    nbytes = _hip.lib().ssad_average_precision_workspace(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    out = torch.empty(3, dtype=torch.float64, device=s.device)
+    _hip.check(_hip.lib().ssad_average_precision(s.data_ptr(), t.data_ptr(), n, ws.data_ptr(), nbytes, out.data_ptr(), _hip.stream()))
+    return float(out[0].item())
+
+
+def pr_curve_gpu(labels, scores):
+    """compute_pr_curve for device-resident scores: (precision fp64, recall fp64, thresholds fp32) as device tensors in sklearn's
+    layout (ssad_pr_curve writes descending thresholds; the end point is appended and the order reversed here)."""
+    from . import _hip
+    s, t = _ap_inputs(labels, scores, "pr_curve_gpu")
+    n, dev = s.numel(), s.device
+    nbytes = _hip.lib().ssad_pr_curve_workspace(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    precision = torch.empty(n, dtype=torch.float64, device=dev)
+    recall = torch.empty(n, dtype=torch.float64, device=dev)
+    thresholds = torch.empty(n, dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    _hip.check(_hip.lib().ssad_pr_curve(s.data_ptr(), t.data_ptr(), n, ws.data_ptr(), nbytes, precision.data_ptr(), recall.data_ptr(),
+                                        thresholds.data_ptr(), count.data_ptr(), _hip.stream()))
+    k = int(count.item())
+    return (torch.cat([precision[:k].flip(0), precision.new_ones(1)]), torch.cat([recall[:k].flip(0), recall.new_zeros(1)]),
+            thresholds[:k].flip(0))
 
 
 def _pro_weights_device(maps, ground_truth_maps):

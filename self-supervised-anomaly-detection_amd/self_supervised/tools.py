@@ -40,7 +40,7 @@ class Evaluator:
         print('>>> start evaluation')
         if self.evaluation_metrics.size == 0:
             print('No metrics selected')
-        bad = [m for m in self.evaluation_metrics if m not in METRICS()]
+        bad = [m for m in self.evaluation_metrics if m not in METRICS() and m != 'ap']          # 'ap': opt-in, not a reference metric
         if bad:
             raise ValueError(f"Wrong metric(s): {bad}; correct metrics list: {METRICS()}")
         targets, scores = output_container.y_true_binary_labels, output_container.anomaly_maps
@@ -49,7 +49,7 @@ class Evaluator:
             scores = torch.flatten(scores, 0, -1)
         on_gpu = scores.is_cuda
         for m in self.evaluation_metrics:
-            if m != 'auroc' and ((m == 'f1-score') == patch_level):
+            if m not in ('auroc', 'ap') and ((m == 'f1-score') == patch_level):
                 raise ValueError(f"'{m}' not a valid metric for '{'patch' if patch_level else 'image'}-level' mode")
         if on_gpu:
             # maps still on the device (straight from tools.upsample): every sort-bound metric runs there (csrc/auroc.hip) --
@@ -69,6 +69,8 @@ class Evaluator:
                 self.curves['pro'] = (fprs, pros)
             if 'iou' in self.evaluation_metrics:
                 self.scores.iou = mtr.compute_iou_gpu(scores, targets_dev, threshold)
+            if 'ap' in self.evaluation_metrics:
+                self.scores.AP = mtr.average_precision_gpu(targets_dev, scores)
         else:
             targets, scores = targets.detach().cpu(), scores.detach().cpu()
             threshold = self._get_threshold(scores, targets)
@@ -86,6 +88,8 @@ class Evaluator:
                 self.curves['pro'] = (fprs, pros)
             if 'iou' in self.evaluation_metrics:
                 self.scores.iou = mtr.compute_iou(scores, targets, threshold)
+            if 'ap' in self.evaluation_metrics:
+                self.scores.AP = mtr.compute_average_precision(targets, scores)
         if outputs_dir:
             os.makedirs(outputs_dir, exist_ok=True)
             with open(os.path.join(outputs_dir, subject + ('_pixel' if patch_level else '_image') + '_scores.json'), 'w') as f:
@@ -885,6 +889,21 @@ def image_auroc(output: ModelOutputsContainer) -> float:
     return float(mtr.compute_auc(fpr, tpr))
 
 
+def _average_precision(targets, scores) -> float:
+    """Average precision on the device when the scores are there (csrc/auroc.hip), else on the host -- as Evaluator chooses."""
+    if scores.is_cuda:
+        return mtr.average_precision_gpu(torch.as_tensor(targets).to(scores.device), scores)
+    return mtr.compute_average_precision(torch.as_tensor(targets).detach().cpu(), scores.detach().cpu())
+
+
+def image_ap(output: ModelOutputsContainer) -> float:
+    """Image average precision of a patch-level run, beside image_auroc: the labels against `output.image_scores`."""
+    scores = output.image_scores
+    if scores is None:
+        raise ValueError("image_ap: the output carries no image_scores (tools.inference(..., image_scores='max' | 'reweighted'))")
+    return _average_precision(output.y_true_binary_labels, scores)
+
+
 def gradcam_maps(model: PeraNet, images: Tensor, y_hat: Tensor, chunk: int = 64) -> Tensor:
     """Image-level localisation (src/evaluator.py:268-282 of the reference): a Grad-CAM saliency of the predicted class
     for every image predicted anomalous (y_hat != 0), an all-zero map otherwise; NaNs of constant maps become 0.
@@ -908,7 +927,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
           upsample_sigma: float = 4.0, dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-          index_options: dict = None, bank_dtype: str = 'float32', gallery: int = None):
+          index_options: dict = None, bank_dtype: str = 'float32', average_precision: bool = False, gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
@@ -916,14 +935,18 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
     `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe`, `index_options` and `bank_dtype` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
-    `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps)."""
+    `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps).
+    `average_precision=True` (patch level) writes one more table in the same way, patch_ap.csv: the pixel AP of the upsampled maps
+    (`pixel_ap`) and, with `image_scores` set, the image AP (`image_ap`, tools.image_ap)."""
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
                    gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype)
+    if average_precision and not patch_localization:
+        raise ValueError("sweep: average_precision=True needs patch_localization=True (patch_ap.csv holds the pixel AP)")
     rank, world = world_info()
     mine = [c for i, c in enumerate(categories) if i % world == rank]
-    rows, image_rows = {}, {}
+    rows, image_rows, ap_rows = {}, {}, {}
     score_kw = {} if image_scores is None else {"image_scores": image_scores, "neighbours": neighbours}
     if localization != 'patches':
         score_kw["localization"] = localization
@@ -954,6 +977,10 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         if patch_localization:
             out.anomaly_maps = upsample(out.anomaly_maps, int(out.ground_truths.shape[-1]), verbose=False, method=upsample_method,
                                         sigma=upsample_sigma)      # stays on the device: the Evaluator's GPU metrics
+        if average_precision:
+            ap_rows[subject] = {'pixel_ap': _average_precision(out.ground_truths.reshape(-1), out.anomaly_maps.reshape(-1))}
+            if image_scores is not None:
+                ap_rows[subject]['image_ap'] = image_ap(out)
         ev = Evaluator(evaluation_metrics=[m for m in metrics if (m != 'f1-score') == patch_localization or m == 'auroc'])
         ev.evaluate(out, subject, sub_out, patch_level=patch_localization)
         rows[subject] = {k: v for k, v in vars(ev.scores).items() if v is not None}
@@ -965,6 +992,9 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         if image_scores is not None:
             dist.all_gather_object(parts, image_rows)
             image_rows = {k: v for part in parts for k, v in part.items()}
+        if average_precision:
+            dist.all_gather_object(parts, ap_rows)
+            ap_rows = {k: v for part in parts for k, v in part.items()}
     cols = sorted({k for r in rows.values() for k in r})
     table = {c: [float(rows[s].get(c, float('nan'))) for s in categories] for c in cols}
     for c in cols:
@@ -981,4 +1011,11 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
             col = [float(image_rows[s]) for s in categories]
             idf = mtr.metrics_to_dataframe({'image_auroc': col + [float(np.nanmean(col))]}, list(categories) + ['average'])
             mtr.export_dataframe(idf, tables_output + 'csv/', 'patch_image_auroc.csv')
+        if average_precision:
+            ap_table = {}
+            for c in ('pixel_ap',) + (('image_ap',) if image_scores is not None else ()):
+                col = [float(ap_rows[s][c]) for s in categories]
+                ap_table[c] = col + [float(np.nanmean(col))]
+            adf = mtr.metrics_to_dataframe(ap_table, list(categories) + ['average'])
+            mtr.export_dataframe(adf, tables_output + 'csv/', 'patch_ap.csv')
     return df
