@@ -591,8 +591,8 @@ int ssad_l2h_knn_index_split(const void* xh, const float* x_sq, const void* bank
  *   of ssad_row_sqnorms (lane-strided fma chain, xor butterfly): a pair's bits do not depend on Q or T.  Q <= 65535.
  * ssad_l2_knn_gallery / _index: ssad_l2_knn_fused / ssad_l2_knn_index with the bank of query image q restricted to the row blocks
  *   [g P, (g + 1) P), g = gallery[q][0 .. K - 1] (int32 bank-image ids).  Grid (ceil(P / 128), Q, S): a query tile never straddles two
- *   images, a bank tile never two blocks.  A (query, bank row) pair gets the bits the whole-bank kernels give it: same tile, K order,
- *   norms and d2 = fmaxf((qn + bn) - 2 dot, 0).  idx holds GLOBAL bank rows, equal d2 go to the smaller global row.  An entry outside
+ *   images, a bank tile never two blocks.  A (query, bank row) pair gets the bits the whole-bank kernels give it: the same tile functions
+ *   (csrc/knn_tile.h) -- K order, norms and d2 = fmaxf((qn + bn) - 2 dot, 0).  idx holds GLOBAL bank rows, equal d2 go to the smaller global row.  An entry outside
  *   0 .. T - 1 is skipped, never dereferenced; a query left with fewer than k candidates gets out = +inf, the missing slots of the
  *   index form (+inf, -1).  S >= 1 splits the K entries; S > 1 needs part ([S][Q P][3] floats / 64-bit keys, 8-byte aligned) and a
  *   merge launch.  out, dist and idx are the same bits for every S and on every call.  D % 32 == 0, D <= 65536, k in 1..3,

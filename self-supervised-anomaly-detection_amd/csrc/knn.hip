@@ -6,7 +6,7 @@
 // knn_mean: the chain wrote and re-read N x R floats (2.4 GB for the 1 M pixels of a WideResNet-50 layer1 scale).  Every
 // intermediate value is formed by the same expression in the same order as in that chain (x / ||x|| per element; the k-order of the
 // MFMA chain; the three smallest distances added smallest first), so the scores are bit-identical to it.
-#include "common.h"
+#include "knn_tile.h"
 
 namespace {
 
@@ -14,8 +14,7 @@ namespace {
 // 16 bank rows of ONE query (column r) and the three smallest distances are kept straight from the accumulators, branch-free -- no
 // trip of every tile through LDS and no scalar scan (round 4: the LDS epilogue was 2.4 of the 6.3 ms of the 1 M-query WideResNet-50
 // layer1 call, the one-row-at-a-time norm prologue another ~2 ms; tools/knn_probe.py).
-constexpr int BB = 128, BQ = 128, BK = 32, LDK = BK + 4, TB = 2, TQ = 2, NT = 256;      // bank rows x queries per workgroup tile
-constexpr int STAGE = (BB + BQ) * LDK;          // floats
+// The tile's constants and the selection (keep3) are knn_tile.h's, which the Euclidean kernels share.
 
 struct KnnParams {
     const float* x;       // [N][D] queries (not normalised)
@@ -24,13 +23,6 @@ struct KnnParams {
     int64_t N;
     int D, R, k;
 };
-
-// a <= b <= c are the three smallest so far; v joins them (no branches: min / max only)
-__device__ __forceinline__ void keep3(float v, float& a, float& b, float& c) {
-    c = fminf(c, fmaxf(b, v));
-    b = fminf(b, fmaxf(a, v));
-    a = fminf(a, v);
-}
 
 __global__ __launch_bounds__(NT, 2) void cosine_knn_fused_kernel(KnnParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -205,8 +197,6 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_fused_kernel(KnnParams p) {
 //
 // Operands are staged with buffer loads (gde.hip's mahalanobis_fused_kernel): a scalar base per K-step, one 32-bit offset
 // per staged row, rows past N or R read zeros -- no per-row pointer select in the matrix loop.
-constexpr unsigned OOB = 0x80000000u;   // size given to the buffers: offsets from here on read zeros
-constexpr int SRD3 = 0x00020000;        // raw buffer, 32-bit data format
 
 struct KnnSplitParams {
     const float* x;       // [N][D] queries (not normalised)
@@ -396,22 +386,6 @@ __global__ void cosine_knn_merge_kernel(const float* __restrict__ part, float* _
 // past R carry the all-ones key.  Matrix loop, K order, staging and the place of a bank row in its tile are the split kernel's, so
 // the distances are the bits the mean kernels form.  Grid (ceil(N / 128), S): with S = 1 the k pairs go straight out (the one-launch
 // form), else the three keys go to part [S][N][3] and cosine_knn_index_merge_kernel merges them.
-typedef unsigned long long u64;
-constexpr u64 NOKEY = ~0ull;
-
-__device__ __forceinline__ u64 umin64(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a < b ? b : a; }
-// a < b < c are the three smallest keys so far; v joins them (keep3 on keys)
-__device__ __forceinline__ void keep3k(u64 v, u64& a, u64& b, u64& c) {
-    c = umin64(c, umax64(b, v));
-    b = umin64(b, umax64(a, v));
-    a = umin64(a, v);
-}
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int o) {
-    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-    return ((u64)hi << 32) | lo;
-}
-
 struct KnnIndexParams {
     const float* x;       // [N][D] queries (not normalised)
     const float* bank;    // [R][D] bank rows, L2-normalised
@@ -555,7 +529,7 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_index_kernel(KnnIndexParams 
                     float d = 1.f - acc[i][j][e];
                     d = fminf(fmaxf(d, 0.f), 2.f);
                     const u64 key = ((u64)__float_as_uint(d) << 32) | (unsigned)row;
-                    keep3k(ok ? key : NOKEY, best[j][0], best[j][1], best[j][2]);
+                    keep3(ok ? key : NOKEY, best[j][0], best[j][1], best[j][2]);
                 }
             }
         }
@@ -565,10 +539,10 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_index_kernel(KnnIndexParams 
     u64* M = (u64*)lds;                         // [2 wq][TQ][32][3]
 #pragma unroll
     for (int j = 0; j < TQ; ++j) {
-        const u64 oa = shfl_xor64(best[j][0], 32), ob = shfl_xor64(best[j][1], 32), oc = shfl_xor64(best[j][2], 32);
-        keep3k(oa, best[j][0], best[j][1], best[j][2]);
-        keep3k(ob, best[j][0], best[j][1], best[j][2]);
-        keep3k(oc, best[j][0], best[j][1], best[j][2]);
+        const u64 oa = shfl_xor_any(best[j][0], 32), ob = shfl_xor_any(best[j][1], 32), oc = shfl_xor_any(best[j][2], 32);
+        keep3(oa, best[j][0], best[j][1], best[j][2]);
+        keep3(ob, best[j][0], best[j][1], best[j][2]);
+        keep3(oc, best[j][0], best[j][1], best[j][2]);
         if (wb == 1 && h == 0) {
             u64* m = M + ((wq * TQ + j) * 32 + r) * 3;
             m[0] = best[j][0]; m[1] = best[j][1]; m[2] = best[j][2];
@@ -580,9 +554,9 @@ __global__ __launch_bounds__(NT, 2) void cosine_knn_index_kernel(KnnIndexParams 
         for (int j = 0; j < TQ; ++j) {
             const u64* m = M + ((wq * TQ + j) * 32 + r) * 3;
             u64 a = best[j][0], b = best[j][1], c = best[j][2];
-            keep3k(m[0], a, b, c);
-            keep3k(m[1], a, b, c);
-            keep3k(m[2], a, b, c);
+            keep3(m[0], a, b, c);
+            keep3(m[1], a, b, c);
+            keep3(m[2], a, b, c);
             const int64_t row = m0 + (wq * TQ + j) * 32 + r;
             if (row < p.N) {
                 if (gridDim.y == 1) {
@@ -603,9 +577,9 @@ __global__ void cosine_knn_index_merge_kernel(KnnIndexParams p, int S) {
     u64 a = NOKEY, b = NOKEY, c = NOKEY;
     for (int s = 0; s < S; ++s) {
         const u64* t = p.part + ((int64_t)s * p.N + n) * 3;
-        keep3k(t[0], a, b, c);
-        keep3k(t[1], a, b, c);
-        keep3k(t[2], a, b, c);
+        keep3(t[0], a, b, c);
+        keep3(t[1], a, b, c);
+        keep3(t[2], a, b, c);
     }
     write_pairs(p, n, a, b, c);
 }

@@ -2,39 +2,20 @@
 // beside the whole-bank search of knn_l2.hip): the bank rows are clustered into nlist cells, stored cell after cell, and a query
 // meets the rows of its nprobe nearest cells only.
 //   ssad_segment_means    k-means' update step: the mean of the rows of every cell, ssad_group_means for groups of any length;
-//   ssad_l2_knn_ivf       the search: knn_l2.hip's kernel with an INDIRECT query side -- a workgroup takes one cell and up to 128 of
+//   ssad_l2_knn_ivf       the search: knn_l2.hip's search with an INDIRECT query side -- a workgroup takes one cell and up to 128 of
 //   / _index              the (query, probe slot) pairs that name it, gathers those queries by row while staging, walks the cell's
 //                         rows and leaves every pair's three best (squared-distance bits << 32 | original bank row) keys; a second
 //                         kernel merges the nprobe triples of a query, takes the roots and writes the mean or (dist, idx).
-// The tile, the K order, the norms' summation order, the d2 expression and the min / max selection are copies of l2_knn_kernel
-// (knn_l2.hip): a (query, bank row) pair gets the bits it gets there, whichever tile it falls into and whoever shares that tile.
-#include "common.h"
+// The search kernel keeps the tile's norm prologue, K loop, epilogue and tail written out in place -- built on the shared functions
+// (dot_tile, tile_select, tile_tail) it measured 1.3-1.9 % slower than this form, beyond the run-to-run spread -- on knn_tile.h's
+// constants and selection.  The text follows the header's functions line for line: the same tile, K order, norm order and d2
+// expression, so a (query, bank row) pair gets the bits l2_knn_kernel gives it, whichever tile it falls into.
+#include "knn_tile.h"
 
 namespace {
 
-constexpr int BB = 128, BQ = 128, BK = 32, LDK = BK + 4, TB = 2, TQ = 2, NT = 256;      // knn_l2.hip's tile: bank rows x queries
-constexpr int STAGE = (BB + BQ) * LDK;          // floats
 constexpr int LDS_BYTES = (2 * STAGE + BQ + BB + BB + 2 * BQ) * 4;      // stages, norms, the tile's original rows, pair ids and query rows
-constexpr unsigned OOB = 0x80000000u;   // size given to the bank buffer: offsets from here on read zeros
-constexpr int SRD3 = 0x00020000;        // raw buffer, 32-bit data format
-
-typedef unsigned long long u64;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr u64 NOKEY = ~0ull;
-
-__device__ __forceinline__ u64 umin64(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a < b ? b : a; }
-__device__ __forceinline__ void keep3(u64 v, u64& a, u64& b, u64& c) {
-    c = umin64(c, umax64(b, v));
-    b = umin64(b, umax64(a, v));
-    a = umin64(a, v);
-}
-__device__ __forceinline__ u64 shfl_xor_any(u64 v, int o) {
-    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-    return ((u64)hi << 32) | lo;
-}
-// d2 >= 0: its bits order like an unsigned integer, so the key's unsigned order is the lexicographic (d2, original row) order
-__device__ __forceinline__ u64 make_key(float d2, int row) { return ((u64)__float_as_uint(d2) << 32) | (unsigned)row; }
 
 // ================================================ k-means' update step ================================================
 
@@ -99,8 +80,8 @@ struct IvfParams {
 // that cell -- and scores their queries against the cell's rows [offsets[cell], offsets[cell + 1]) in 128-row tiles; rows past the
 // cell's end are masked (they read zeros and make no candidate), never taken from the next cell.  Slots past cnt stage query row 0 and
 // are never written.  Everything a value read from device memory addresses is checked first: the cell, the pair range, the pair ids
-// and the cell's bounds.  Everything inside a tile is l2_knn_kernel's (knn_l2.hip); the queries are staged with plain 16-byte loads
-// (a row of x is anywhere in a buffer that may exceed the 2 GB an offset of a buffer load reaches).
+// and the cell's bounds.  The tile is knn_tile.h's, written out in place (see the head of this file); the queries are staged with
+// plain 16-byte loads (a row of x is anywhere in a buffer that may exceed the 2 GB an offset of a buffer load reaches).
 __global__ __launch_bounds__(NT, 2) void l2_knn_ivf_kernel(IvfParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* qn_s = lds + 2 * STAGE;              // [BQ] squared norms of the queries
@@ -243,7 +224,7 @@ __global__ __launch_bounds__(NT, 2) void l2_knn_ivf_kernel(IvfParams p) {
 #pragma unroll
                     for (int j = 0; j < TQ; ++j) {
                         const float d2 = fmaxf((qn[j] + bn[c]) - 2.f * acc[i][j][e], 0.f);
-                        keep3(ok ? make_key(d2, row) : NOKEY, best[j][0], best[j][1], best[j][2]);
+                        keep3(ok ? Sel<true>::make(d2, row) : NOKEY, best[j][0], best[j][1], best[j][2]);
                     }
                 }
             }

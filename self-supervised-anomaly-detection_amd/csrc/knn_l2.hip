@@ -4,47 +4,13 @@
 //   |q|^2, |b|^2 one summation order (sqnorm_wave: lane-strided fma, xor butterfly) wherever they are taken, so equal rows give equal bits,
 //   d2           fmaxf((qn + bn) - 2 dot, 0) in the per-tile epilogue; the K loop is knn.hip's, untouched by the metric.
 // Selection runs on d2 (monotone in d); sqrtf is applied to the k winners only.  One kernel template serves the four entry points:
-// mean or (distance, row) keys, one launch (S = 1) or the bank split of ssad_cosine_knn_split with a merge launch.
-#include "common.h"
+// mean or (distance, row) keys, one launch (S = 1) or the bank split of ssad_cosine_knn_split with a merge launch.  The tile itself
+// -- norms, K loop, epilogue, tail, result writers -- is knn_tile.h's; this file walks the bank with it.
+#include "knn_tile.h"
 
 namespace {
 
-constexpr int BB = 128, BQ = 128, BK = 32, LDK = BK + 4, TB = 2, TQ = 2, NT = 256;      // knn.hip's tile: bank rows x queries
-constexpr int STAGE = (BB + BQ) * LDK;          // floats
 constexpr int LDS_BYTES = (2 * STAGE + BQ + BB) * 4;
-constexpr unsigned OOB = 0x80000000u;   // size given to the buffers: offsets from here on read zeros
-constexpr int SRD3 = 0x00020000;        // raw buffer, 32-bit data format
-
-typedef unsigned long long u64;
-constexpr u64 NOKEY = ~0ull;
-
-__device__ __forceinline__ void keep3(float v, float& a, float& b, float& c) {
-    c = fminf(c, fmaxf(b, v));
-    b = fminf(b, fmaxf(a, v));
-    a = fminf(a, v);
-}
-__device__ __forceinline__ u64 umin64(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a < b ? b : a; }
-__device__ __forceinline__ void keep3(u64 v, u64& a, u64& b, u64& c) {
-    c = umin64(c, umax64(b, v));
-    b = umin64(b, umax64(a, v));
-    a = umin64(a, v);
-}
-__device__ __forceinline__ float shfl_xor_any(float v, int o) { return __shfl_xor(v, o); }
-__device__ __forceinline__ u64 shfl_xor_any(u64 v, int o) {
-    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-    return ((u64)hi << 32) | lo;
-}
-
-// sum x^2 of one row by one wave -- THE summation order of every squared norm in this file: lane l takes elements l, l + 64, ... in
-// an fma chain, then an xor butterfly (every lane ends with the sum).  The prologue below runs the same chain for eight rows at once.
-__device__ __forceinline__ float sqnorm_wave(const float* __restrict__ row, int D, int lane) {
-    float s = 0.f;
-    for (int k = lane; k < D; k += 64) s = __builtin_fmaf(row[k], row[k], s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
 
 __global__ __launch_bounds__(NT) void row_sqnorms_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t N, int D) {
     const int lane = threadIdx.x & 63;
@@ -66,219 +32,53 @@ struct L2Params {
     int D, R, rows_per, k;
 };
 
-template <bool KEYS> struct Sel;
-template <> struct Sel<false> {
-    typedef float T;
-    static __device__ __forceinline__ float none() { return INFINITY; }
-    static __device__ __forceinline__ float make(float d2, int) { return d2; }
-};
-template <> struct Sel<true> {
-    typedef u64 T;
-    static __device__ __forceinline__ u64 none() { return NOKEY; }
-    // d2 >= 0: its bits order like an unsigned integer, so the key's unsigned order is the lexicographic (d2, row) order
-    static __device__ __forceinline__ u64 make(float d2, int row) { return ((u64)__float_as_uint(d2) << 32) | (unsigned)row; }
-};
-
-// the k winners of query `row`: the mean of their roots, smallest first, or the (root, bank row) pairs
-__device__ __forceinline__ void write_result(const L2Params& p, int64_t row, float a, float b, float c) {
-    float s = sqrtf(a);
-    if (p.k > 1) s += sqrtf(b);
-    if (p.k > 2) s += sqrtf(c);
-    p.out[row] = s / (float)p.k;
-}
-__device__ __forceinline__ void write_result(const L2Params& p, int64_t row, u64 a, u64 b, u64 c) {
-    const u64 key[3] = {a, b, c};
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        if (j < p.k) {
-            p.dist[row * p.k + j] = sqrtf(__uint_as_float((unsigned)(key[j] >> 32)));
-            p.idx[row * p.k + j] = (int)(unsigned)key[j];
-        }
-    }
-}
-
 // Grid (ceil(N / 128), S): workgroup (t, s) scores queries [128 t, 128 t + 128) against the bank rows [s rows_per, (s + 1) rows_per).
-// Matrix loop, staging (buffer loads: rows past N or R read zeros) and the place of a bank row in its tile are
-// cosine_knn_index_kernel's (knn.hip); the operands go to LDS as they are.
+// Both operands are staged by buffer loads: rows past N or R read zeros.
 template <bool KEYS>
 __global__ __launch_bounds__(NT, 2) void l2_knn_kernel(L2Params p) {
     typedef typename Sel<KEYS>::T T;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* qn_s = lds + 2 * STAGE;              // [BQ] squared norms of the queries
     float* bn_s = qn_s + BQ;                    // [BB] squared norms of the current bank tile
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wb = wave >> 1, wq = wave & 1;    // 64-row bank block / 64-query block of this wave
+    const TileThread t{};
     const int64_t m0 = (int64_t)blockIdx.x * BQ;
-    const int sc = tid & 7, sr = tid >> 3;      // staging: 16-byte chunk sc of rows sr + 32 i
 
-    // ---- squared query norms: sqnorm_wave's order, eight rows in flight per wave (knn.hip's prologue); rows past N give 0 ----
-    for (int base = wave; base < BQ; base += 32) {
-        float s[8];
-        const float* q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int64_t row = m0 + base + 4 * u;
-            q[u] = row < p.N ? p.x + row * p.D : nullptr;
-            s[u] = 0.f;
-        }
-        for (int k = lane; k < p.D; k += 64) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = q[u] ? q[u][k] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s[u] = __builtin_fmaf(v[u], v[u], s[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            float t = s[u];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-            if (lane == 0) qn_s[base + 4 * u] = t;
-        }
-    }
+    tile_sqnorms<true>(qn_s, p.D, t, [&](int s) { return m0 + s < p.N ? p.x + (m0 + s) * p.D : nullptr; });     // rows past N give 0
     unsigned qoff[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qoff[i] = m0 + sr + 32 * i < p.N ? (unsigned)(((sr + 32 * i) * p.D + sc * 4) * 4) : OOB;
+    stage_offsets(qoff, m0, p.N, p.D, t);
     const float* xblk = p.x + m0 * p.D;
 
-    // running three smallest of this lane's queries (column r of its TQ query blocks) over the bank rows it has seen
     T best[TQ][3];
 #pragma unroll
     for (int j = 0; j < TQ; ++j) best[j][0] = best[j][1] = best[j][2] = Sel<KEYS>::none();
-    const int nks = p.D / BK;
     const int64_t r_begin = (int64_t)blockIdx.y * p.rows_per;
     const int r_end = (int)(r_begin + p.rows_per < p.R ? r_begin + p.rows_per : p.R);
 
     for (int n0 = (int)(r_begin < p.R ? r_begin : p.R); n0 < r_end; n0 += BB) {
         unsigned boff[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) boff[i] = n0 + sr + 32 * i < p.R ? (unsigned)(((sr + 32 * i) * p.D + sc * 4) * 4) : OOB;
-        const float* bblk = p.bank + (int64_t)n0 * p.D;
+        stage_offsets(boff, n0, p.R, p.D, t);
         f32x16 acc[TB][TQ];
-#pragma unroll
-        for (int i = 0; i < TB; ++i)
-#pragma unroll
-            for (int j = 0; j < TQ; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-        f32x4 rq[4], rb[4];
-        auto load = [&](int ks) {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xblk + ks * BK), 0, (int)OOB, SRD3);
-            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(bblk + ks * BK), 0, (int)OOB, SRD3);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                rq[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, qoff[i], 0, 0));
-                rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, boff[i], 0, 0));
-            }
-        };
-        auto store = [&](float* st) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                *(f32x4*)(st + (sr + 32 * i) * LDK + sc * 4) = rb[i];                   // bank rows: the tile's M side
-                *(f32x4*)(st + BB * LDK + (sr + 32 * i) * LDK + sc * 4) = rq[i];        // queries: its N side
-            }
-        };
-        __syncthreads();                        // every wave has left the previous bank tile's last stage and its norms
-        load(0);
-        if (tid < BB) bn_s[tid] = n0 + tid < p.R ? p.bsq[n0 + tid] : 0.f;
-        store(lds);
-        __syncthreads();
-        for (int ks = 0; ks < nks; ++ks) {
-            const float* cur = lds + (ks & 1) * STAGE;
-            if (ks + 1 < nks) load(ks + 1);
-            const float* As = cur + (wb * 32 * TB + r) * LDK + h * 4;
-            const float* Bs = cur + BB * LDK + (wq * 32 * TQ + r) * LDK + h * 4;
-#pragma unroll
-            for (int kk = 0; kk < BK / 8; ++kk) {
-                f32x4 a[TB], b[TQ];
-#pragma unroll
-                for (int i = 0; i < TB; ++i) a[i] = *(const f32x4*)(As + i * 32 * LDK + kk * 8);
-#pragma unroll
-                for (int j = 0; j < TQ; ++j) b[j] = *(const f32x4*)(Bs + j * 32 * LDK + kk * 8);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < TB; ++i)
-#pragma unroll
-                        for (int j = 0; j < TQ; ++j) acc[i][j] = mfma32(a[i][e], b[j][e], acc[i][j]);
-            }
-            if (ks + 1 < nks) store(lds + ((ks + 1) & 1) * STAGE);
-            __syncthreads();
-        }
-        // ---- the finished tile: register e of lane (r, h) in block (i, j) is bank row row0 + (e & 3) + 8 (e >> 2) of query column r ----
-        float qn[TQ];
-#pragma unroll
-        for (int j = 0; j < TQ; ++j) qn[j] = qn_s[(wq * TQ + j) * 32 + r];
-#pragma unroll
-        for (int i = 0; i < TB; ++i) {
-            const int l0 = (wb * TB + i) * 32 + 4 * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bn = *(const f32x4*)(bn_s + l0 + 8 * g);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int e = 4 * g + c;
-                    const int row = n0 + l0 + c + 8 * g;
-                    const bool ok = row < p.R;
-#pragma unroll
-                    for (int j = 0; j < TQ; ++j) {
-                        const float d2 = fmaxf((qn[j] + bn[c]) - 2.f * acc[i][j][e], 0.f);
-                        keep3(ok ? Sel<KEYS>::make(d2, row) : Sel<KEYS>::none(), best[j][0], best[j][1], best[j][2]);
-                    }
-                }
-            }
-        }
+        dot_tile(acc, lds, t, p.bank + (int64_t)n0 * p.D, boff, p.D / BK,
+                 [&](int ks, int i) { return buffer_load16(xblk + ks * BK, qoff[i]); },
+                 [&] { if (t.tid < BB) bn_s[t.tid] = n0 + t.tid < p.R ? p.bsq[n0 + t.tid] : 0.f; });
+        tile_select<KEYS>(acc, qn_s, bn_s, t, best, [&](int l, int c) { return RowId{n0 + l + c < p.R, n0 + l + c}; });
     }
-    // ---- a query's candidates sit in the two lane halves of two waves (wb = 0, 1): halves by shuffle, waves through LDS ----
-    __syncthreads();                            // the stages are dead
-    T* M = (T*)lds;                             // [2 wq][TQ][32][3]
-#pragma unroll
-    for (int j = 0; j < TQ; ++j) {
-        const T oa = shfl_xor_any(best[j][0], 32), ob = shfl_xor_any(best[j][1], 32), oc = shfl_xor_any(best[j][2], 32);
-        keep3(oa, best[j][0], best[j][1], best[j][2]);
-        keep3(ob, best[j][0], best[j][1], best[j][2]);
-        keep3(oc, best[j][0], best[j][1], best[j][2]);
-        if (wb == 1 && h == 0) {
-            T* m = M + ((wq * TQ + j) * 32 + r) * 3;
-            m[0] = best[j][0]; m[1] = best[j][1]; m[2] = best[j][2];
-        }
-    }
-    __syncthreads();
-    if (wb == 0 && h == 0) {
-#pragma unroll
-        for (int j = 0; j < TQ; ++j) {
-            const T* m = M + ((wq * TQ + j) * 32 + r) * 3;
-            T a = best[j][0], b = best[j][1], c = best[j][2];
-            keep3(m[0], a, b, c);
-            keep3(m[1], a, b, c);
-            keep3(m[2], a, b, c);
-            const int64_t row = m0 + (wq * TQ + j) * 32 + r;
-            if (row < p.N) {
-                if (gridDim.y == 1) {
-                    write_result(p, row, a, b, c);
-                } else {
-                    T* o = (T*)p.part + ((int64_t)blockIdx.y * p.N + row) * 3;
-                    o[0] = a; o[1] = b; o[2] = c;
-                }
-            }
-        }
-    }
+    tile_tail(best, lds, t, [&](int slot, T a, T b, T c) {
+        const int64_t row = m0 + slot;
+        if (row >= p.N) return;
+        if (gridDim.y == 1) write_result(p, row, a, b, c);
+        else put3((T*)p.part + ((int64_t)blockIdx.y * p.N + row) * 3, a, b, c);
+    });
 }
 
-// the three smallest of the S triples of query n (min / max selection: any order gives the same three), then the one-launch epilogue
+// the three smallest of the S triples of query n, then the one-launch epilogue
 template <bool KEYS>
 __global__ void l2_knn_merge_kernel(L2Params p, int S) {
     typedef typename Sel<KEYS>::T T;
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= p.N) return;
     T a = Sel<KEYS>::none(), b = a, c = a;
-    for (int s = 0; s < S; ++s) {
-        const T* t = (const T*)p.part + ((int64_t)s * p.N + n) * 3;
-        keep3(t[0], a, b, c);
-        keep3(t[1], a, b, c);
-        keep3(t[2], a, b, c);
-    }
+    merge_splits((const T*)p.part, S, p.N, n, a, b, c);
     write_result(p, n, a, b, c);
 }
 

@@ -7,37 +7,14 @@
 // h: fp32 -> fp16 round to nearest even, saturating at +-65504, results below 2^-14 in magnitude flushed to signed zero -- no half
 // ever holds inf, NaN or a subnormal.  Selection, tie rule, keys, split and merge are l2_knn_kernel's.  The matrix loop holds no
 // conversion and no norm prologue: both operands arrive as halves, both norm vectors as floats.
-#include "common.h"
+#include "knn_tile.h"
 
 namespace {
 
-constexpr int BB = 128, BQ = 128, BK = 64, LDK = BK + 8, TB = 2, TQ = 2, NT = 256;      // bank rows x queries x halves per K step
-constexpr int STAGE = (BB + BQ) * LDK;          // halves; 144-byte rows: the 16 rows of a ds_read_b128 lane group fall on 16 distinct
-                                                // 16-byte slots of the 256-byte bank row (36 r mod 64 runs over the multiples of 4)
-constexpr int LDS_BYTES = 2 * STAGE * 2 + (BQ + BB) * 4;
-constexpr unsigned OOB = 0x80000000u;   // size given to the buffers: offsets from here on read zeros
-constexpr int SRD3 = 0x00020000;        // raw buffer, 32-bit data format
-
-typedef unsigned long long u64;
-constexpr u64 NOKEY = ~0ull;
-
-__device__ __forceinline__ void keep3(float v, float& a, float& b, float& c) {
-    c = fminf(c, fmaxf(b, v));
-    b = fminf(b, fmaxf(a, v));
-    a = fminf(a, v);
-}
-__device__ __forceinline__ u64 umin64(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a < b ? b : a; }
-__device__ __forceinline__ void keep3(u64 v, u64& a, u64& b, u64& c) {
-    c = umin64(c, umax64(b, v));
-    b = umin64(b, umax64(a, v));
-    a = umin64(a, v);
-}
-__device__ __forceinline__ float shfl_xor_any(float v, int o) { return __shfl_xor(v, o); }
-__device__ __forceinline__ u64 shfl_xor_any(u64 v, int o) {
-    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-    return ((u64)hi << 32) | lo;
-}
+// knn_tile.h's tile (BB x BQ, four waves of 2 x 2 accumulators) with a K step of its own
+constexpr int HK = 64, HLDK = HK + 8;           // halves per K step; 144-byte rows: the 16 rows of a ds_read_b128 lane group fall on 16
+constexpr int HSTAGE = (BB + BQ) * HLDK;        // distinct 16-byte slots of the 256-byte bank row (36 r mod 64 runs over the multiples of 4)
+constexpr int LDS_BYTES = 2 * HSTAGE * 2 + (BQ + BB) * 4;
 
 // h: clamp to the largest finite half first (65504 < v < 65520 would round to it anyway, v >= 65520 to inf), round to nearest even,
 // then clear the mantissa of a result whose exponent field is zero (a subnormal half or a zero): signed zero
@@ -82,37 +59,6 @@ struct L2hParams {
     int D, R, rows_per, k;
 };
 
-template <bool KEYS> struct Sel;
-template <> struct Sel<false> {
-    typedef float T;
-    static __device__ __forceinline__ float none() { return INFINITY; }
-    static __device__ __forceinline__ float make(float d2, int) { return d2; }
-};
-template <> struct Sel<true> {
-    typedef u64 T;
-    static __device__ __forceinline__ u64 none() { return NOKEY; }
-    // d2 >= 0: its bits order like an unsigned integer, so the key's unsigned order is the lexicographic (d2, row) order
-    static __device__ __forceinline__ u64 make(float d2, int row) { return ((u64)__float_as_uint(d2) << 32) | (unsigned)row; }
-};
-
-// the k winners of query `row`: the mean of their roots, smallest first, or the (root, bank row) pairs
-__device__ __forceinline__ void write_result(const L2hParams& p, int64_t row, float a, float b, float c) {
-    float s = sqrtf(a);
-    if (p.k > 1) s += sqrtf(b);
-    if (p.k > 2) s += sqrtf(c);
-    p.out[row] = s / (float)p.k;
-}
-__device__ __forceinline__ void write_result(const L2hParams& p, int64_t row, u64 a, u64 b, u64 c) {
-    const u64 key[3] = {a, b, c};
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        if (j < p.k) {
-            p.dist[row * p.k + j] = sqrtf(__uint_as_float((unsigned)(key[j] >> 32)));
-            p.idx[row * p.k + j] = (int)(unsigned)key[j];
-        }
-    }
-}
-
 // Grid (ceil(N / 128), S): workgroup (t, s) scores queries [128 t, 128 t + 128) against the bank rows [s rows_per, (s + 1) rows_per).
 // Four waves, each a 64 x 64 block of the tile (2 x 2 accumulators of v_mfma_f32_32x32x16_f16).  A K step stages 64 halves (128 bytes)
 // of 256 rows -- 16-byte buffer loads: rows past N or R and columns past D (the last step of D = 32 mod 64) read zeros, which add
@@ -123,32 +69,28 @@ template <bool KEYS>
 __global__ __launch_bounds__(NT, 2) void l2h_knn_kernel(L2hParams p) {
     typedef typename Sel<KEYS>::T T;
     extern __shared__ __attribute__((aligned(16))) hf lds[];
-    float* qn_s = (float*)(lds + 2 * STAGE);    // [BQ] squared norms of the queries
+    float* qn_s = (float*)(lds + 2 * HSTAGE);   // [BQ] squared norms of the queries
     float* bn_s = qn_s + BQ;                    // [BB] squared norms of the current bank tile
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wb = wave >> 1, wq = wave & 1;    // 64-row bank block / 64-query block of this wave
+    const TileThread t{};                       // staging: 16-byte chunk sc is 8 halves
     const int64_t m0 = (int64_t)blockIdx.x * BQ;
-    const int sc = tid & 7, sr = tid >> 3;      // staging: 16-byte chunk sc (8 halves) of rows sr + 32 i
 
-    if (tid < BQ) qn_s[tid] = m0 + tid < p.N ? p.xsq[m0 + tid] : 0.f;
+    if (t.tid < BQ) qn_s[t.tid] = m0 + t.tid < p.N ? p.xsq[m0 + t.tid] : 0.f;
     unsigned qoff[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) qoff[i] = m0 + sr + 32 * i < p.N ? (unsigned)(((sr + 32 * i) * p.D + sc * 8) * 2) : OOB;
+    for (int i = 0; i < 4; ++i) qoff[i] = m0 + t.sr + 32 * i < p.N ? (unsigned)(((t.sr + 32 * i) * p.D + t.sc * 8) * 2) : OOB;
     const hf* xblk = p.x + m0 * p.D;
 
-    // running three smallest of this lane's queries (column r of its TQ query blocks) over the bank rows it has seen
     T best[TQ][3];
 #pragma unroll
     for (int j = 0; j < TQ; ++j) best[j][0] = best[j][1] = best[j][2] = Sel<KEYS>::none();
-    const int nks = (p.D + BK - 1) / BK;
+    const int nks = (p.D + HK - 1) / HK;
     const int64_t r_begin = (int64_t)blockIdx.y * p.rows_per;
     const int r_end = (int)(r_begin + p.rows_per < p.R ? r_begin + p.rows_per : p.R);
 
     for (int n0 = (int)(r_begin < p.R ? r_begin : p.R); n0 < r_end; n0 += BB) {
         unsigned boff[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) boff[i] = n0 + sr + 32 * i < p.R ? (unsigned)(((sr + 32 * i) * p.D + sc * 8) * 2) : OOB;
+        for (int i = 0; i < 4; ++i) boff[i] = n0 + t.sr + 32 * i < p.R ? (unsigned)(((t.sr + 32 * i) * p.D + t.sc * 8) * 2) : OOB;
         const hf* bblk = p.bank + (int64_t)n0 * p.D;
         f32x16 acc[TB][TQ];
 #pragma unroll
@@ -159,9 +101,9 @@ __global__ __launch_bounds__(NT, 2) void l2h_knn_kernel(L2hParams p) {
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
         f16x8 rq[4], rb[4];
         auto load = [&](int ks) {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xblk + ks * BK), 0, (int)OOB, SRD3);
-            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(bblk + ks * BK), 0, (int)OOB, SRD3);
-            const bool in = ks * BK + sc * 8 < p.D;     // this chunk's columns exist (D is a multiple of 32, a chunk is 8 wide)
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xblk + ks * HK), 0, (int)OOB, SRD3);
+            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(bblk + ks * HK), 0, (int)OOB, SRD3);
+            const bool in = ks * HK + t.sc * 8 < p.D;   // this chunk's columns exist (D is a multiple of 32, a chunk is 8 wide)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 rq[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, in ? qoff[i] : OOB, 0, 0));
@@ -171,108 +113,53 @@ __global__ __launch_bounds__(NT, 2) void l2h_knn_kernel(L2hParams p) {
         auto store = [&](hf* st) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                *(f16x8*)(st + (sr + 32 * i) * LDK + sc * 8) = rb[i];                   // bank rows: the tile's M side
-                *(f16x8*)(st + BB * LDK + (sr + 32 * i) * LDK + sc * 8) = rq[i];        // queries: its N side
+                *(f16x8*)(st + (t.sr + 32 * i) * HLDK + t.sc * 8) = rb[i];                  // bank rows: the tile's M side
+                *(f16x8*)(st + BB * HLDK + (t.sr + 32 * i) * HLDK + t.sc * 8) = rq[i];      // queries: its N side
             }
         };
         __syncthreads();                        // every wave has left the previous bank tile's last stage and its norms
         load(0);
-        if (tid < BB) bn_s[tid] = n0 + tid < p.R ? p.bsq[n0 + tid] : 0.f;
+        if (t.tid < BB) bn_s[t.tid] = n0 + t.tid < p.R ? p.bsq[n0 + t.tid] : 0.f;
         store(lds);
         __syncthreads();
         for (int ks = 0; ks < nks; ++ks) {
-            const hf* cur = lds + (ks & 1) * STAGE;
+            const hf* cur = lds + (ks & 1) * HSTAGE;
             if (ks + 1 < nks) load(ks + 1);
-            const hf* As = cur + (wb * 32 * TB + r) * LDK + h * 8;
-            const hf* Bs = cur + BB * LDK + (wq * 32 * TQ + r) * LDK + h * 8;
+            const hf* As = cur + (t.wb * 32 * TB + t.r) * HLDK + t.h * 8;
+            const hf* Bs = cur + BB * HLDK + (t.wq * 32 * TQ + t.r) * HLDK + t.h * 8;
 #pragma unroll
-            for (int kk = 0; kk < BK / 16; ++kk) {
+            for (int kk = 0; kk < HK / 16; ++kk) {
                 f16x8 a[TB], b[TQ];
 #pragma unroll
-                for (int i = 0; i < TB; ++i) a[i] = *(const f16x8*)(As + i * 32 * LDK + kk * 16);
+                for (int i = 0; i < TB; ++i) a[i] = *(const f16x8*)(As + i * 32 * HLDK + kk * 16);
 #pragma unroll
-                for (int j = 0; j < TQ; ++j) b[j] = *(const f16x8*)(Bs + j * 32 * LDK + kk * 16);
+                for (int j = 0; j < TQ; ++j) b[j] = *(const f16x8*)(Bs + j * 32 * HLDK + kk * 16);
 #pragma unroll
                 for (int i = 0; i < TB; ++i)
 #pragma unroll
                     for (int j = 0; j < TQ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
             }
-            if (ks + 1 < nks) store(lds + ((ks + 1) & 1) * STAGE);
+            if (ks + 1 < nks) store(lds + ((ks + 1) & 1) * HSTAGE);
             __syncthreads();
         }
-        // ---- the finished tile ----
-        float qn[TQ];
-#pragma unroll
-        for (int j = 0; j < TQ; ++j) qn[j] = qn_s[(wq * TQ + j) * 32 + r];
-#pragma unroll
-        for (int i = 0; i < TB; ++i) {
-            const int l0 = (wb * TB + i) * 32 + 4 * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bn = *(const f32x4*)(bn_s + l0 + 8 * g);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int e = 4 * g + c;
-                    const int row = n0 + l0 + c + 8 * g;
-                    const bool ok = row < p.R;
-#pragma unroll
-                    for (int j = 0; j < TQ; ++j) {
-                        const float d2 = fmaxf((qn[j] + bn[c]) - 2.f * acc[i][j][e], 0.f);
-                        keep3(ok ? Sel<KEYS>::make(d2, row) : Sel<KEYS>::none(), best[j][0], best[j][1], best[j][2]);
-                    }
-                }
-            }
-        }
+        tile_select<KEYS>(acc, qn_s, bn_s, t, best, [&](int l, int c) { return RowId{n0 + l + c < p.R, n0 + l + c}; });
     }
-    // ---- a query's candidates sit in the two lane halves of two waves (wb = 0, 1): halves by shuffle, waves through LDS ----
-    __syncthreads();                            // the stages are dead
-    T* M = (T*)lds;                             // [2 wq][TQ][32][3]
-#pragma unroll
-    for (int j = 0; j < TQ; ++j) {
-        const T oa = shfl_xor_any(best[j][0], 32), ob = shfl_xor_any(best[j][1], 32), oc = shfl_xor_any(best[j][2], 32);
-        keep3(oa, best[j][0], best[j][1], best[j][2]);
-        keep3(ob, best[j][0], best[j][1], best[j][2]);
-        keep3(oc, best[j][0], best[j][1], best[j][2]);
-        if (wb == 1 && h == 0) {
-            T* m = M + ((wq * TQ + j) * 32 + r) * 3;
-            m[0] = best[j][0]; m[1] = best[j][1]; m[2] = best[j][2];
-        }
-    }
-    __syncthreads();
-    if (wb == 0 && h == 0) {
-#pragma unroll
-        for (int j = 0; j < TQ; ++j) {
-            const T* m = M + ((wq * TQ + j) * 32 + r) * 3;
-            T a = best[j][0], b = best[j][1], c = best[j][2];
-            keep3(m[0], a, b, c);
-            keep3(m[1], a, b, c);
-            keep3(m[2], a, b, c);
-            const int64_t row = m0 + (wq * TQ + j) * 32 + r;
-            if (row < p.N) {
-                if (gridDim.y == 1) {
-                    write_result(p, row, a, b, c);
-                } else {
-                    T* o = (T*)p.part + ((int64_t)blockIdx.y * p.N + row) * 3;
-                    o[0] = a; o[1] = b; o[2] = c;
-                }
-            }
-        }
-    }
+    tile_tail(best, lds, t, [&](int slot, T a, T b, T c) {
+        const int64_t row = m0 + slot;
+        if (row >= p.N) return;
+        if (gridDim.y == 1) write_result(p, row, a, b, c);
+        else put3((T*)p.part + ((int64_t)blockIdx.y * p.N + row) * 3, a, b, c);
+    });
 }
 
-// the three smallest of the S triples of query n (min / max selection: any order gives the same three), then the one-launch epilogue
+// the three smallest of the S triples of query n, then the one-launch epilogue
 template <bool KEYS>
 __global__ void l2h_knn_merge_kernel(L2hParams p, int S) {
     typedef typename Sel<KEYS>::T T;
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= p.N) return;
     T a = Sel<KEYS>::none(), b = a, c = a;
-    for (int s = 0; s < S; ++s) {
-        const T* t = (const T*)p.part + ((int64_t)s * p.N + n) * 3;
-        keep3(t[0], a, b, c);
-        keep3(t[1], a, b, c);
-        keep3(t[2], a, b, c);
-    }
+    merge_splits((const T*)p.part, S, p.N, n, a, b, c);
     write_result(p, n, a, b, c);
 }
 
