@@ -583,6 +583,23 @@ int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, con
                        int D, int R, int k, void* stream);
 int ssad_l2h_knn_index_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
                              int* idx, int64_t N, int D, int R, int k, int S, void* stream);
+/* The flat Euclidean search for k = 4..32 (csrc/knn_topk.hip; the entry points above keep k = 1..3): the same tile, dot loops, norms
+ * and d2 expression, so a (query, bank row) pair has the d2 bits of ssad_l2_knn_index / ssad_l2h_knn_index; a query keeps the k
+ * smallest (d2 bits << 32 | row) keys.  Keys are unique: the result is the first k entries of a stable ascending sort of (d2, row)
+ * whatever the split count S and the batch a query sits in, the same bits on every call.  No atomics.
+ * ssad_l2_knn_topk_index: dist [N][k] = sqrtf(d2) of the winners, idx [N][k] int32, ascending, equal d2 to the smaller row.
+ * ssad_l2_knn_topk: out[n] = (dist[n][0] + dist[n][1] + ... + dist[n][k - 1]) / k, added in that order in fp32.
+ * ssad_l2h_knn_topk / _index: the same on rounded rows (arguments as ssad_l2h_knn_fused).
+ * S bank splits, 1 <= S <= 65535 (1: one launch; else a merge launch follows); part [S][N][k] 64-bit keys, caller-owned, 8-byte
+ * aligned, unused (may be null) for S = 1.  D % 32 == 0, D <= 65536, 4 <= k <= 32, k <= R. */
+int ssad_l2_knn_topk(const float* x, const float* bank, const float* bank_sq, void* part, float* out, int64_t N, int D, int R, int k,
+                     int S, void* stream);
+int ssad_l2_knn_topk_index(const float* x, const float* bank, const float* bank_sq, void* part, float* dist, int* idx, int64_t N, int D,
+                           int R, int k, int S, void* stream);
+int ssad_l2h_knn_topk(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* out, int64_t N,
+                      int D, int R, int k, int S, void* stream);
+int ssad_l2h_knn_topk_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
+                            int* idx, int64_t N, int D, int R, int k, int S, void* stream);
 /* SPADE's image-conditioned gallery for the Euclidean kNN (csrc/knn_gallery.hip; Cohen & Hoshen 2020): a query image is scored against
  * the rows of K bank images only.  Queries x [Q P][D] and bank [T P][D] hold P rows per image, image after image.
  * ssad_group_means: out[g][c] = mean_i x[g P + i][c], the image descriptor: summed in fp64 in row order 0 .. P - 1, rounded once to

@@ -270,4 +270,104 @@ __device__ __forceinline__ void merge_splits(const T* part, int S, int64_t N, in
     }
 }
 
+// ================================================ the k smallest keys, k = 4 .. 32 (knn_topk.hip) ================================================
+// L[0] < L[1] < ... < L[CAP - 1] are the CAP smallest keys so far (NOKEY where fewer were met); v joins them.  Keys are unique (one
+// per bank row), so the CAP smallest of a set do not depend on the order in which its members arrive.  Branch-free, indices known at
+// compile time (the list stays in registers): slot i takes its lower neighbour when v goes below that, else the smaller of itself and
+// v.  A v that is not below L[CAP - 1] -- NOKEY never is -- changes nothing.
+template <int CAP>
+__device__ __forceinline__ void topk_insert(u64 (&L)[CAP], u64 v) {
+#pragma unroll
+    for (int i = CAP - 1; i > 0; --i) L[i] = v < L[i - 1] ? L[i - 1] : umin64(L[i], v);
+    L[0] = umin64(L[0], v);
+}
+
+// the ascending keys src[0], src[stride], ... (count of them) join L; a wave stops at the first key that no lane can use
+template <int CAP>
+__device__ __forceinline__ void topk_merge(u64 (&L)[CAP], const u64* src, int stride, int count) {
+#pragma unroll 1
+    for (int i = 0; i < count; ++i) {
+        const u64 v = src[(int64_t)i * stride];
+        if (!__any(v < L[CAP - 1])) break;
+        topk_insert(L, v);
+    }
+}
+
+// tile_select for a list: the finished tile joins the CAP smallest keys of this lane's queries.  d2 is tile_select's expression on the
+// same accumulators, so a (query, bank row) pair has the bits the k <= 3 kernels give it.  A candidate passes when its key is below
+// the list's last entry as the tile begins (a bit of `mask`); after the first tiles almost none does, and a wave runs the insertion
+// network once per round for the lowest passing candidate of every lane -- as many rounds as its busiest lane has candidates.
+template <int CAP, class RowOf>
+__device__ __forceinline__ void tile_select_topk(const f32x16 (&acc)[TB][TQ], const float* qn_s, const float* bn_s, const TileThread& t,
+                                                 u64 (&L)[TQ][CAP], RowOf rowof) {
+    static_assert(TB * 16 == 32, "a candidate mask is 32 bits");
+#pragma unroll
+    for (int j = 0; j < TQ; ++j) {
+        const float qn = qn_s[(t.wq * TQ + j) * 32 + t.r];
+        const u64 worst = L[j][CAP - 1];
+        float d[TB * 16];
+        unsigned mask = 0;
+#pragma unroll
+        for (int i = 0; i < TB; ++i) {
+            const int l0 = (t.wb * TB + i) * 32 + 4 * t.h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 bn = *(const f32x4*)(bn_s + l0 + 8 * g);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const RowId row = rowof(l0 + 8 * g, c);
+                    const float d2 = fmaxf((qn + bn[c]) - 2.f * acc[i][j][4 * g + c], 0.f);
+                    d[i * 16 + 4 * g + c] = d2;
+                    if (row.ok && Sel<true>::make(d2, row.id) < worst) mask |= 1u << (i * 16 + 4 * g + c);
+                }
+            }
+        }
+        while (__any(mask != 0)) {
+            const int e = mask ? __builtin_ctz(mask) : 0;       // candidate e = 16 i + 4 g + c
+            float d2 = d[0];
+#pragma unroll
+            for (int q = 1; q < TB * 16; ++q) d2 = e == q ? d[q] : d2;
+            const RowId row = rowof((t.wb * TB + (e >> 4)) * 32 + 4 * t.h + 8 * ((e >> 2) & 3), e & 3);
+            topk_insert(L[j], mask ? Sel<true>::make(d2, row.id) : NOKEY);
+            mask &= mask - 1;
+        }
+    }
+}
+
+// tile_tail for lists: lane halves, then waves, through LDS (the stages are dead; 2 x 128 x CAP keys, key i of slot s at [i][s]).
+// emit(slot, j): L[j] holds the CAP smallest keys of query slot `slot` of the tile, once per slot.
+template <int CAP, class Emit>
+__device__ __forceinline__ void tile_tail_topk(u64 (&L)[TQ][CAP], void* lds, const TileThread& t, Emit emit) {
+    static_assert(2 * CAP * BQ * 8 <= 2 * STAGE * 4, "the lists of two waves fit into the stages");
+    u64* M = (u64*)lds;                         // [2 wb][CAP][BQ]
+    __syncthreads();
+    if (t.h == 1) {
+#pragma unroll
+        for (int j = 0; j < TQ; ++j)
+#pragma unroll
+            for (int i = 0; i < CAP; ++i) M[(t.wb * CAP + i) * BQ + (t.wq * TQ + j) * 32 + t.r] = L[j][i];
+    }
+    __syncthreads();
+    if (t.h == 0) {
+#pragma unroll
+        for (int j = 0; j < TQ; ++j) topk_merge(L[j], M + t.wb * CAP * BQ + (t.wq * TQ + j) * 32 + t.r, BQ, CAP);
+    }
+    __syncthreads();
+    if (t.wb == 1 && t.h == 0) {
+#pragma unroll
+        for (int j = 0; j < TQ; ++j)
+#pragma unroll
+            for (int i = 0; i < CAP; ++i) M[i * BQ + (t.wq * TQ + j) * 32 + t.r] = L[j][i];
+    }
+    __syncthreads();
+    if (t.wb == 0 && t.h == 0) {
+#pragma unroll
+        for (int j = 0; j < TQ; ++j) {
+            const int slot = (t.wq * TQ + j) * 32 + t.r;
+            topk_merge(L[j], M + slot, BQ, CAP);
+            emit(slot, j);
+        }
+    }
+}
+
 }  // namespace

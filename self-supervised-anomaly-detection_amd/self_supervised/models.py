@@ -545,6 +545,30 @@ def check_bank_dtype(bank_dtype, metric='euclidean', index='flat', gallery=None,
     return bank_dtype
 
 
+N_NEIGHBORS_MAX = 32       # ops.TOPK_MAX: the widest list of csrc/knn_topk.hip
+N_NEIGHBORS_EVERYWHERE = 3  # what every search kernel selects (keep3)
+
+
+def check_n_neighbors(n_neighbors, metric='cosine', index='flat', gallery=None):
+    """ValueError unless `n_neighbors` is an int in 1..32 -- the k of the patch score (sklearn's n_neighbors, PatchCore's
+    anomaly_scorer_num_nn) -- and, above 3, metric='euclidean', index='flat' and gallery=None: 1..3 run on every path, 4..32 on the
+    flat Euclidean search only (csrc/knn_topk.hip; either bank_dtype)."""
+    if isinstance(n_neighbors, (bool, np.bool_)) or not isinstance(n_neighbors, (int, np.integer)) or \
+            not 1 <= n_neighbors <= N_NEIGHBORS_MAX:
+        raise ValueError(f"n_neighbors must be an int in 1..{N_NEIGHBORS_MAX}, got {n_neighbors!r}")
+    if n_neighbors <= N_NEIGHBORS_EVERYWHERE:
+        return int(n_neighbors)
+    supported = (f"n_neighbors above {N_NEIGHBORS_EVERYWHERE} is supported by the flat Euclidean search only (metric='euclidean', "
+                 "index='flat', gallery=None; bank_dtype 'float32' or 'float16')")
+    if metric != 'euclidean':
+        raise ValueError(f"n_neighbors={n_neighbors} needs metric='euclidean', got metric={metric!r}: {supported}")
+    if index != 'flat':
+        raise ValueError(f"n_neighbors={n_neighbors} needs index='flat', got index={index!r}: {supported}")
+    if gallery is not None:
+        raise ValueError(f"n_neighbors={n_neighbors} needs gallery=None, got gallery={gallery!r}: {supported}")
+    return int(n_neighbors)
+
+
 INDEXES = ('flat', 'ivf')
 IVF_OPTIONS = ('iters', 'seed', 'train_rows')
 IVF_MAX_NLIST = 4096
@@ -635,13 +659,20 @@ class AnomalyDetector(Detector):
     squared norms of the rounded rows; the fp32 rows are dropped.  Queries are rounded the same way per call and every distance is
     that BETWEEN THE ROUNDED ROWS, on the fp16 matrix cores with fp32 accumulation (ops.l2h_knn_fused / l2h_knn_index) -- it differs
     from the fp32 search's by the rounding of the operands (relative 2^-11 per element).  Needs metric='euclidean', index='flat' and
-    gallery=None; works at both levels and with a coreset; image_scores takes 'max' only."""
+    gallery=None; works at both levels and with a coreset; image_scores takes 'max' only.
+
+    `n_neighbors` (default 3, the reference's; sklearn's n_neighbors, PatchCore's anomaly_scorer_num_nn, SPADE's kappa): the k of the
+    score -- the mean distance to the k nearest bank rows -- kept as `self.k` and read by ``predict``, the threshold of ``fit``, the
+    patch scores inside ``image_scores`` and the default of ``kneighbors``.  1..3 run on every path with the kernels those paths
+    have.  4..32 need metric='euclidean', index='flat' and gallery=None (either bank_dtype; csrc/knn_topk.hip, ops.l2_topk_mean /
+    l2h_topk_mean): a pair's distance keeps the bits of the k <= 3 search, so the first three neighbours are those of n_neighbors=3.
+    Cosine, gallery and IVF searches for k > 3 are a follow-up.  A bank of fewer rows than n_neighbors raises.  Not to be confused
+    with the `neighbours` of ``image_scores``: that is the b of PatchCore's eq. 6-7, the size of the reweighting neighbourhood."""
 
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
                  coreset_dim: int = 128, metric: str = 'cosine', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-                 index_options: dict = None, bank_dtype: str = 'float32', gallery: int = None) -> None:
+                 index_options: dict = None, bank_dtype: str = 'float32', n_neighbors: int = 3, gallery: int = None) -> None:
         super().__init__(patch_level, batch, num_patches)
-        self.k = 3
         self.bank = None
         self.bank_sq = None             # metric='euclidean': squared norms of the bank rows (ops.row_sqnorms)
         self.metric = check_metric(metric)
@@ -661,7 +692,13 @@ class AnomalyDetector(Detector):
         self.index_options = dict(index_options or {})
         self.ivf = None                 # index='ivf' after fit: perm, offsets, centroids, cent_sq, nlist, nprobe (bank: sorted by cell)
         self.bank_dtype = check_bank_dtype(bank_dtype, self.metric, self.index, self.gallery)
-        self._rows32 = None             # bank_dtype='float16', inside fit with a coreset: the fp32 rows the selection runs on
+        self.k = check_n_neighbors(n_neighbors, self.metric, self.index, self.gallery)      # the one place n_neighbors is kept
+        self._rows32 = None            # bank_dtype='float16', inside fit with a coreset: the fp32 rows the selection runs on
+
+    @property
+    def n_neighbors(self) -> int:
+        """The k of the score, as the constructor took it: `self.k` is where it is kept (the reference's attribute)."""
+        return self.k
 
     def _whole_images(self, what, rows: int) -> int:
         if rows < 1 or rows % self.patches:
@@ -686,7 +723,7 @@ class AnomalyDetector(Detector):
         return groups
 
     def _after_bank(self) -> None:
-        self.k = 3                      # as the reference's fit sets it; read by _scores for the threshold
+        self.k = self.n_neighbors       # as the reference's fit sets it (the literal 3 there); read by _scores for the threshold
         if self.gallery is not None:
             self.bank_desc = ops.group_means(self.bank, self.patches)
         if self.coreset is not None:
@@ -768,6 +805,8 @@ class AnomalyDetector(Detector):
             state["bank_dtype"] = self.bank_dtype       # `bank` holds the rounded rows as torch.float16
         if self.gallery is not None:
             state["gallery"] = self.gallery
+        if self.n_neighbors != 3:
+            state["n_neighbors"] = self.n_neighbors     # absent = 3: states written before the option still load
         if self.index == 'ivf':
             if self.ivf is None:
                 raise ValueError("state: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
@@ -783,6 +822,9 @@ class AnomalyDetector(Detector):
         if state.get("bank_dtype", 'float32') != self.bank_dtype:
             raise ValueError(f"load_state: the bank was fitted with bank_dtype={state.get('bank_dtype', 'float32')!r}, this detector has "
                              f"{self.bank_dtype!r}")
+        if state.get("n_neighbors", 3) != self.n_neighbors:
+            raise ValueError(f"load_state: the bank was fitted with n_neighbors={state.get('n_neighbors', 3)!r}, this detector has "
+                             f"{self.n_neighbors!r}")
         if self.bank_dtype == 'float16':
             # the halves are fixed points of h, so rounding their fp32 values again returns them and the norms in the fit's order
             self.bank, self.bank_sq = ops.rows_to_half(self._dev(state["bank"]))
@@ -818,6 +860,8 @@ class AnomalyDetector(Detector):
     def _scores(self, x):
         if self.bank_dtype == 'float16':
             self._check_width("predict", x.shape[1])
+            if self.k > 3:
+                return ops.l2h_topk_mean(x, self.bank, self.bank_sq, self.k)
             return ops.l2h_knn_fused(x, self.bank, self.bank_sq, self.k)
         if self.gallery is not None:
             self._check_width("predict", x.shape[1])
@@ -830,6 +874,8 @@ class AnomalyDetector(Detector):
             return ops.l2_knn_ivf(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"], self.k)
         if self.metric == 'euclidean':
             self._check_width("predict", x.shape[1])
+            if self.k > 3:
+                return ops.l2_topk_mean(x, self.bank, self.bank_sq, self.k)
             return ops.l2_knn_fused(x, self.bank, self.bank_sq, self.k)
         if x.shape[1] % 32 == 0 and 1 <= self.k <= 3:
             # normalise + similarity GEMM + k smallest distances in one kernel: no N x bank matrix in HBM (csrc/knn.hip)
@@ -844,7 +890,7 @@ class AnomalyDetector(Detector):
 
     def kneighbors(self, x: Tensor, k: int = None):
         """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
-        idx [N][k] int64), the k (default self.k; 1..3) nearest bank rows of every row of x by the detector's metric, nearest first, equal
+        idx [N][k] int64), the k (default self.k; 1..32 on the flat Euclidean paths, 1..3 elsewhere) nearest bank rows of every row of x by the detector's metric, nearest first, equal
         distances to the smaller row.  idx indexes self.bank (after the split and the coreset).  Works at both levels.  With a gallery
         x holds whole images and the neighbours are taken among the rows of each image's gallery (idx still indexes self.bank).
         With index='ivf' the neighbours are taken among the rows of the probed cells and idx holds the caller's rows, as index='flat'
@@ -854,20 +900,20 @@ class AnomalyDetector(Detector):
         x = self._dev(x)
         if x.shape[1] % 32:
             raise ValueError(f"kneighbors: the index kernel needs an embedding width that is a multiple of 32, got {x.shape[1]}")
+        k = self.k if k is None else int(k)
         if self.bank_dtype == 'float16':
-            dist, idx = ops.l2h_knn_index(x, self.bank, self.bank_sq, self.k if k is None else k)
+            dist, idx = (ops.l2h_topk_index if k > 3 else ops.l2h_knn_index)(x, self.bank, self.bank_sq, k)
         elif self.gallery is not None:
             gallery, _ = self.retrieve(x)
-            dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, self.k if k is None else k)
+            dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, k)
         elif self.index == 'ivf':
             if self.ivf is None:
                 raise ValueError("kneighbors: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
-            dist, idx = ops.l2_knn_ivf_index(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"],
-                                             self.k if k is None else k)
+            dist, idx = ops.l2_knn_ivf_index(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"], k)
         elif self.metric == 'euclidean':
-            dist, idx = ops.l2_knn_index(x, self.bank, self.bank_sq, self.k if k is None else k)
+            dist, idx = (ops.l2_topk_index if k > 3 else ops.l2_knn_index)(x, self.bank, self.bank_sq, k)
         else:
-            dist, idx = ops.cosine_knn_index(x, self.bank, self.k if k is None else k)
+            dist, idx = ops.cosine_knn_index(x, self.bank, k)
         return dist, idx.long()
 
     def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = 9, scores: Tensor = None) -> Tensor:

@@ -986,6 +986,80 @@ def l2h_knn_index(x, bank_h, bank_sq, k=3, splits=None):
     return dist, idx
 
 
+TOPK_MIN, TOPK_MAX = 4, 32     # k of the list kernels (csrc/knn_topk.hip); 1..3 stay with the kernels above
+
+
+def _topk_args(name, x, bank, bank_sq, k, splits, half):
+    n, d = x.shape
+    r = bank.shape[0]
+    k = int(k)
+    _check_l2_width(name, d)
+    if half and bank.dtype != torch.float16:
+        raise ValueError(f"{name}: the bank must be [R][{d}] float16 rows with their [R] squared norms (rows_to_half)")
+    if bank.shape[1] != d or bank_sq.shape[0] != r:
+        raise ValueError(f"{name}: the bank must be [R][{d}] rows with their [R] squared norms, got {tuple(bank.shape)} and "
+                         f"{tuple(bank_sq.shape)}")
+    if not TOPK_MIN <= k <= TOPK_MAX:
+        raise ValueError(f"{name}: k must lie in {TOPK_MIN}..{TOPK_MAX} (1..3: the l2_knn / l2h_knn functions), got {k}")
+    if r < k:
+        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"{name}: splits must be >= 1, got {s}")
+    part = torch.empty((s, n, k), device=x.device, dtype=torch.int64) if s > 1 else None   # (squared-distance bits << 32 | row) keys
+    return n, d, r, k, s, part
+
+
+def l2_topk_index(x, bank, bank_sq, k, splits=None):
+    """l2_knn_index for k in 4..32 (csrc/knn_topk.hip ssad_l2_knn_topk_index): (dist [N][k] float32, idx [N][k] int32), the first k
+    entries of a stable ascending sort of the (squared distance, bank row) pairs of every query; a pair's squared distance has
+    l2_knn_index's bits, so the first three columns are l2_knn_index(k=3).  `splits` as in l2_knn_fused; the same bits for every S
+    and every batch a query sits in."""
+    n, d, r, k, s, part = _topk_args("l2_topk_index", x, bank, bank_sq, k, splits, False)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    _run("l2_topk_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + 2 * n * k) + 16.0 * (s > 1) * s * n * k,
+         lambda: _hip.lib().ssad_l2_knn_topk_index(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part, True, torch.int64), _hip.ptr(dist),
+                                                   _hip.ptr(idx, dtype=torch.int32), n, d, r, k, s, _hip.stream()))
+    return dist, idx
+
+
+def l2_topk_mean(x, bank, bank_sq, k, splits=None):
+    """l2_knn_fused for k in 4..32 (csrc/knn_topk.hip ssad_l2_knn_topk) -> [N] mean of the k smallest Euclidean distances: the fp32
+    sum of l2_topk_index's dist row, added smallest first one after the other, divided by k -- those bits."""
+    n, d, r, k, s, part = _topk_args("l2_topk_mean", x, bank, bank_sq, k, splits, False)
+    out = _new((n,), x)
+    _run("l2_topk_mean", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n) + 16.0 * (s > 1) * s * n * k,
+         lambda: _hip.lib().ssad_l2_knn_topk(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part, True, torch.int64), _hip.ptr(out), n, d, r, k, s,
+                                             _hip.stream()))
+    return out
+
+
+def l2h_topk_index(x, bank_h, bank_sq, k, splits=None):
+    """l2h_knn_index for k in 4..32 (arguments as l2h_knn_fused; csrc/knn_topk.hip ssad_l2h_knn_topk_index): l2_topk_index between
+    the rounded rows, a pair's squared distance with l2h_knn_index's bits."""
+    n, d, r, k, s, part = _topk_args("l2h_topk_index", x, bank_h, bank_sq, k, splits, True)
+    xh, xsq = rows_to_half(x)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    _run("l2h_topk_index", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + n + 2 * n * k) + 16.0 * (s > 1) * s * n * k,
+         lambda: _hip.lib().ssad_l2h_knn_topk_index(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(part, True, torch.int64),
+                                                    _hip.ptr(dist), _hip.ptr(idx, dtype=torch.int32), n, d, r, k, s, _hip.stream()))
+    return dist, idx
+
+
+def l2h_topk_mean(x, bank_h, bank_sq, k, splits=None):
+    """l2h_knn_fused for k in 4..32 (csrc/knn_topk.hip ssad_l2h_knn_topk): the sequential fp32 sum of l2h_topk_index's dist row
+    divided by k."""
+    n, d, r, k, s, part = _topk_args("l2h_topk_mean", x, bank_h, bank_sq, k, splits, True)
+    xh, xsq = rows_to_half(x)
+    out = _new((n,), x)
+    _run("l2h_topk_mean", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + 2 * n) + 16.0 * (s > 1) * s * n * k,
+         lambda: _hip.lib().ssad_l2h_knn_topk(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(part, True, torch.int64),
+                                              _hip.ptr(out), n, d, r, k, s, _hip.stream()))
+    return out
+
+
 def l2_from_dots(sim, qsq, bsq):
     """sim [Q][R] dot products, qsq [Q], bsq [R] squared norms -> [Q][R] SQUARED Euclidean distances max(qsq + bsq - 2 sim, 0)
     (csrc/knn_l2.hip ssad_l2_from_dots; the kNN kernels' expression)."""

@@ -437,6 +437,16 @@ def _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores
     return check_bank_dtype(bank_dtype, metric, index, gallery, image_scores)
 
 
+def _check_n_neighbors(n_neighbors, detector, metric, index, gallery):
+    """The n_neighbors option of the kNN detector (models.check_n_neighbors): the k of the patch score, 1..3 on every path, 4..32 on
+    the flat Euclidean search; either level, localization, dense_features, bank and bank_dtype, with or without a coreset."""
+    if detector != 'knn':
+        if n_neighbors != 3:
+            raise ValueError(f"n_neighbors={n_neighbors!r} applies to detector='knn' only, got detector={detector!r}")
+        return 3
+    return models.check_n_neighbors(n_neighbors, metric, index, gallery)
+
+
 def _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery=None, index='flat'):
     """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
     scores and their nearest bank rows, which the image level and the Gaussian do not have."""
@@ -515,7 +525,8 @@ def _pyramid_columns(detector, det_kw):
 
 
 def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options,
-                   gallery=None, dense_features='local', index='flat', nlist=None, nprobe=8, index_options=None, bank_dtype='float32'):
+                   gallery=None, dense_features='local', index='flat', nlist=None, nprobe=8, index_options=None, bank_dtype='float32',
+                   n_neighbors=3):
     """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
     _check_detector(detector)
     _check_metric(metric, detector)
@@ -527,6 +538,7 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
     _check_index(index, nlist, nprobe, index_options, detector, metric, gallery)
     _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery, index)
     _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores)
+    n_neighbors = _check_n_neighbors(n_neighbors, detector, metric, index, gallery)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
     if dense_features == 'pyramid' and detector == 'padim':
         det_kw.update(preselected=True, width=PYRAMID_WIDTH)     # the model writes the chosen columns only (_pyramid_columns)
@@ -541,6 +553,8 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
         det_kw.update(index=index, nlist=nlist, nprobe=nprobe, index_options=index_options)
     if bank_dtype != 'float32':
         det_kw["bank_dtype"] = bank_dtype
+    if n_neighbors != 3:
+        det_kw["n_neighbors"] = n_neighbors
     return models.DETECTORS[detector], det_kw
 
 
@@ -745,7 +759,8 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
               coreset=None, image_scores: str = None, neighbours: int = 9,
               localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine',
               dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-              index_options: dict = None, bank_dtype: str = 'float32', gallery: int = None) -> ModelOutputsContainer:
+              index_options: dict = None, bank_dtype: str = 'float32', n_neighbors: int = 3,
+              gallery: int = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -785,9 +800,14 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     (AnomalyDetector(bank_dtype='float16'); faiss' useFloat16): bank rows and queries ARE ROUNDED TO fp16, so the distances are those
     between the rounded rows; the bank takes half the memory, on every rank and in the broadcast.  Needs detector='knn',
     metric='euclidean', index='flat' and gallery=None; either level, localization, dense_features and bank, with or without a
-    coreset (selected on the fp32 rows); image_scores 'max' only."""
+    coreset (selected on the fp32 rows); image_scores 'max' only.
+    `n_neighbors`: the k of the kNN score (AnomalyDetector(n_neighbors=k); sklearn's n_neighbors, PatchCore's anomaly_scorer_num_nn,
+    SPADE's kappa), default 3 as the reference: maps, threshold and the patch scores under `image_scores` are the mean distance to
+    the k nearest bank rows.  1..3 on every path; 4..32 need metric='euclidean', index='flat' and gallery=None (either bank_dtype).
+    'knn' only.  Not the `neighbours` above, which sizes the reweighting neighbourhood of image_scores='reweighted'."""
     cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
-                                 neighbours, detector_options, gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype)
+                                 neighbours, detector_options, gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype,
+                                 n_neighbors)
     del TIMELINE[:]
     print('>>> initializing inference')
     plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
@@ -927,13 +947,14 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           detector: str = 'knn', bank: str = 'reference', coreset=None, image_scores: str = None, neighbours: int = 9,
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
           upsample_sigma: float = 4.0, dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-          index_options: dict = None, bank_dtype: str = 'float32', average_precision: bool = False, gallery: int = None):
+          index_options: dict = None, bank_dtype: str = 'float32', average_precision: bool = False, n_neighbors: int = 3,
+          gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe`, `index_options` and `bank_dtype` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe`, `index_options`, `bank_dtype` and `n_neighbors` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
     `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps).
     `average_precision=True` (patch level) writes one more table in the same way, patch_ap.csv: the pixel AP of the upsampled maps
@@ -941,7 +962,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
-                   gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype)
+                   gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype, n_neighbors)
     if average_precision and not patch_localization:
         raise ValueError("sweep: average_precision=True needs patch_localization=True (patch_ap.csv holds the pixel AP)")
     rank, world = world_info()
@@ -962,6 +983,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw.update(index=index, nlist=nlist, nprobe=nprobe, index_options=index_options)
     if bank_dtype != 'float32':
         score_kw["bank_dtype"] = bank_dtype
+    if n_neighbors != 3:
+        score_kw["n_neighbors"] = n_neighbors
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
