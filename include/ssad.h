@@ -583,6 +583,25 @@ int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, con
                        int D, int R, int k, void* stream);
 int ssad_l2h_knn_index_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
                              int* idx, int64_t N, int D, int R, int k, int S, void* stream);
+/* An 8-bit scalar-quantised bank for the flat Euclidean search (csrc/knn_l2_int8.hip; faiss' IndexScalarQuantizer, QT_8bit_uniform):
+ * one affine code (lo, s) for the whole bank, c(x) = rint(min(max((x - lo) * inv_s, 0), 255)) - 128 in fp32 in that order (to nearest
+ * even; NaN -> -128), stored as int8.  The distance is that BETWEEN THE CODES plus the query's clamp loss:
+ * d = sqrtf(fmaf(s2, (float)D2, excess)), D2 = sum_j (c(q_j) - c(b_j))^2 = (qsq + bsq) - 2 <c(q), c(b)> in int32 -- exact, the dot
+ * product on v_mfma_i32_32x32x32_i8 -- and s2 = s s rounded once by the caller.
+ * ssad_rows_to_int8: codes [N][D] int8 (8-byte aligned; x 16-byte aligned), sq[n] = sum_j codes[n][j]^2 (int32) and excess[n] =
+ *   sum_j (x[n][j] - min(max(x[n][j], lo), fmaf(255, s, lo)))^2 in fp32 in ssad_row_sqnorms' order (0 for a row inside the coded
+ *   range, NaN for a row with a NaN), one pass.  D % 32 == 0, D <= 32768 (D 255^2 must fit int32).
+ * ssad_l2q_knn_fused / _index: ssad_l2_knn_fused / _index on codes, k = 1..3 -- xq [N][D] and bankq [R][D] codes (16-byte aligned),
+ *   x_sq [N], x_excess [N] and bank_sq [R] from ssad_rows_to_int8.  S bank splits: 1 = one launch (part unused); S > 1 = part
+ *   [S][N][3] uint32 (fused) or 64-bit keys (index), caller-owned, 8-byte aligned, and a merge launch.  idx: equal D2 to the smaller
+ *   row -- the first k entries of a stable sort of (D2, row), exactly.  The same bits for every S and on every call; out is the
+ *   sequential fp32 sum of the index form's dist row divided by k.  Every error leaves the outputs untouched. */
+int ssad_rows_to_int8(const float* x, void* codes, int* sq, float* excess, int64_t N, int D, float lo, float inv_s, float s,
+                      void* stream);
+int ssad_l2q_knn_fused(const void* xq, const int* x_sq, const float* x_excess, const void* bankq, const int* bank_sq, void* part,
+                       float* out, int64_t N, int D, int R, int k, int S, float s2, void* stream);
+int ssad_l2q_knn_index(const void* xq, const int* x_sq, const float* x_excess, const void* bankq, const int* bank_sq, void* part,
+                       float* dist, int* idx, int64_t N, int D, int R, int k, int S, float s2, void* stream);
 /* The flat Euclidean search for k = 4..32 (csrc/knn_topk.hip; the entry points above keep k = 1..3): the same tile, dot loops, norms
  * and d2 expression, so a (query, bank row) pair has the d2 bits of ssad_l2_knn_index / ssad_l2h_knn_index; a query keeps the k
  * smallest (d2 bits << 32 | row) keys.  Keys are unique: the result is the first k entries of a stable ascending sort of (d2, row)

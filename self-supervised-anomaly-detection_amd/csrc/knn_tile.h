@@ -31,6 +31,13 @@ __device__ __forceinline__ void keep3(u64 v, u64& a, u64& b, u64& c) {
     b = umin64(b, umax64(a, v));
     a = umin64(a, v);
 }
+// 32-bit integer squared distances (knn_l2_int8.hip)
+__device__ __forceinline__ void keep3(unsigned v, unsigned& a, unsigned& b, unsigned& c) {
+    c = min(c, max(b, v));
+    b = min(b, max(a, v));
+    a = min(a, v);
+}
+__device__ __forceinline__ unsigned shfl_xor_any(unsigned v, int o) { return __shfl_xor(v, o); }
 __device__ __forceinline__ float shfl_xor_any(float v, int o) { return __shfl_xor(v, o); }
 __device__ __forceinline__ u64 shfl_xor_any(u64 v, int o) {
     const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);

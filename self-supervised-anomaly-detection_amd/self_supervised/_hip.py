@@ -65,6 +65,10 @@ SIGNATURES = {
     "ssad_l2h_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2h_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2h_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    # an 8-bit scalar-quantised bank for the flat Euclidean search (csrc/knn_l2_int8.hip)
+    "ssad_rows_to_int8": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_f, _c_f, _c_f, _c_fp],
+    "ssad_l2q_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_fp],
+    "ssad_l2q_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_fp],
     # the flat Euclidean search for k = 4..32 (csrc/knn_topk.hip)
     "ssad_l2_knn_topk": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2_knn_topk_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],

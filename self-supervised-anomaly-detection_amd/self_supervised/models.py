@@ -521,17 +521,32 @@ def check_gallery(gallery, metric='euclidean', coreset=None):
     return int(gallery)
 
 
-BANK_DTYPES = ('float32', 'float16')
+BANK_DTYPES = ('float32', 'float16', 'int8')
 
 
-def check_bank_dtype(bank_dtype, metric='euclidean', index='flat', gallery=None, image_scores=None):
-    """ValueError unless `bank_dtype` is 'float32' (default: the bank rows as they are) or 'float16' (the flat Euclidean search with
-    half-precision operands, csrc/knn_l2_half.hip: faiss' useFloat16) with metric='euclidean' (the half kernel is Euclidean),
+def check_bank_dtype(bank_dtype, metric='euclidean', index='flat', gallery=None, image_scores=None, n_neighbors=3):
+    """ValueError unless `bank_dtype` is 'float32' (default: the bank rows as they are), 'float16' (the flat Euclidean search with
+    half-precision operands, csrc/knn_l2_half.hip: faiss' useFloat16) or 'int8' (the same search on an 8-bit scalar-quantised bank,
+    csrc/knn_l2_int8.hip: faiss' QT_8bit_uniform) -- the latter two with metric='euclidean' (their kernels are Euclidean),
     index='flat' and gallery=None (it is the whole-bank search) and `image_scores` None or 'max' ('reweighted' takes direct fp32
-    differences to bank rows, which a half bank no longer has)."""
+    differences to bank rows, which a half or coded bank no longer has); 'int8' also with `n_neighbors` in 1..3."""
     if bank_dtype not in BANK_DTYPES:
         raise ValueError(f"bank_dtype must be one of {BANK_DTYPES}, got {bank_dtype!r}")
     if bank_dtype == 'float32':
+        return bank_dtype
+    if bank_dtype == 'int8':
+        if metric != 'euclidean':
+            raise ValueError(f"bank_dtype='int8' needs metric='euclidean' (the int8 kernel is Euclidean), got metric={metric!r}")
+        if index != 'flat':
+            raise ValueError(f"bank_dtype='int8' needs index='flat' (it is the search over the whole bank), got index={index!r}")
+        if gallery is not None:
+            raise ValueError("bank_dtype='int8' needs gallery=None: the gallery kernel reads fp32 bank rows")
+        if image_scores not in (None, 'max'):
+            raise ValueError(f"bank_dtype='int8' takes image_scores None or 'max', got {image_scores!r}: 'reweighted' takes direct fp32 "
+                             "differences to bank rows, which the coded bank no longer holds")
+        if isinstance(n_neighbors, (int, np.integer)) and not isinstance(n_neighbors, (bool, np.bool_)) and n_neighbors > 3:
+            raise ValueError(f"bank_dtype='int8' supports n_neighbors in 1..3, got {n_neighbors}: 4..{N_NEIGHBORS_MAX} need bank_dtype "
+                             "'float32' or 'float16' (a top-k search on codes is a follow-up)")
         return bank_dtype
     if metric != 'euclidean':
         raise ValueError(f"bank_dtype='float16' needs metric='euclidean' (the half-precision kernel is Euclidean), got metric={metric!r}")
@@ -659,7 +674,14 @@ class AnomalyDetector(Detector):
     squared norms of the rounded rows; the fp32 rows are dropped.  Queries are rounded the same way per call and every distance is
     that BETWEEN THE ROUNDED ROWS, on the fp16 matrix cores with fp32 accumulation (ops.l2h_knn_fused / l2h_knn_index) -- it differs
     from the fp32 search's by the rounding of the operands (relative 2^-11 per element).  Needs metric='euclidean', index='flat' and
-    gallery=None; works at both levels and with a coreset; image_scores takes 'max' only.
+    gallery=None; works at both levels and with a coreset; image_scores takes 'max' only.  'int8' = AN 8-BIT SCALAR-QUANTISED BANK
+    (faiss' IndexScalarQuantizer, QT_8bit_uniform): after the coreset selection `fit` takes lo / hi, the smallest / largest element
+    of the rows that are kept, and keeps `quant` = (lo, s), s = (hi - lo) / 255, `bank` = the codes rint((x - lo) / s) - 128 as
+    torch.int8 -- a quarter of the fp32 bytes -- and `bank_sq` = the sums of their squares as torch.int32 (ops.int8_quantiser,
+    ops.rows_to_int8); the fp32 rows are dropped.  Queries are coded the same way per call and every distance is that BETWEEN THE
+    CODES, sqrt(s^2 D2 + excess) with D2 the exact integer squared code distance on the int8 matrix cores and excess what the clamp
+    to [lo, hi] took from the query (ops.l2q_knn_fused / l2q_knn_index): it differs from the fp32 distance by at most s sqrt(D) for
+    a query inside the bank's range and never exceeds it by more.  Same conditions as 'float16', and n_neighbors in 1..3.
 
     `n_neighbors` (default 3, the reference's; sklearn's n_neighbors, PatchCore's anomaly_scorer_num_nn, SPADE's kappa): the k of the
     score -- the mean distance to the k nearest bank rows -- kept as `self.k` and read by ``predict``, the threshold of ``fit``, the
@@ -691,9 +713,11 @@ class AnomalyDetector(Detector):
         self.nprobe = int(nprobe)
         self.index_options = dict(index_options or {})
         self.ivf = None                 # index='ivf' after fit: perm, offsets, centroids, cent_sq, nlist, nprobe (bank: sorted by cell)
-        self.bank_dtype = check_bank_dtype(bank_dtype, self.metric, self.index, self.gallery)
+        self.bank_dtype = check_bank_dtype(bank_dtype, self.metric, self.index, self.gallery, None, n_neighbors)
         self.k = check_n_neighbors(n_neighbors, self.metric, self.index, self.gallery)      # the one place n_neighbors is kept
-        self._rows32 = None            # bank_dtype='float16', inside fit with a coreset: the fp32 rows the selection runs on
+        self._rows32 = None            # bank_dtype='float16' / 'int8', inside fit with a coreset: the fp32 rows the selection runs on
+        if self.bank_dtype == 'int8':
+            self.quant = None           # after fit: (lo, s) of the bank's 8-bit code (ops.int8_quantiser)
 
     @property
     def n_neighbors(self) -> int:
@@ -731,9 +755,12 @@ class AnomalyDetector(Detector):
             m = coreset_size(self.coreset, r)
             if m < r:
                 sel, rad = coreset_select(self.bank if self._rows32 is None else self._rows32, m, self.coreset_dim)
-                self.bank = self.bank.index_select(0, sel).contiguous()
-                if self.bank_sq is not None:
-                    self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
+                if self.bank_dtype == 'int8':
+                    self._quantise(self._rows32.index_select(0, sel).contiguous())     # the code spans the rows that are kept
+                else:
+                    self.bank = self.bank.index_select(0, sel).contiguous()
+                    if self.bank_sq is not None:
+                        self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
                 self.coreset_rows = (sel, rad)
             self.coreset_counts = (int(self.bank.shape[0]), r)
         if self.index == 'ivf':
@@ -769,7 +796,7 @@ class AnomalyDetector(Detector):
             raise ValueError(f"{what}: metric='euclidean' needs an embedding width that is a multiple of 32, got {d}")
 
     def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
-        if self.bank_dtype != 'float16' or self.coreset is None:
+        if self.bank_dtype == 'float32' or self.coreset is None:
             return super().fit(embeddings, split, groups)
         self._rows32 = True             # fit_bank keeps the fp32 rows for the coreset selection of _after_bank
         try:
@@ -785,6 +812,12 @@ class AnomalyDetector(Detector):
             self.bank, self.bank_sq = ops.rows_to_half(rows)
             self._rows32 = rows if self._rows32 is not None else None
             return
+        if self.bank_dtype == 'int8':
+            self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
+            rows = self._dev(bank)
+            self._quantise(rows)
+            self._rows32 = rows if self._rows32 is not None else None
+            return
         if self.metric == 'euclidean':
             self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
             if self.gallery is not None:
@@ -795,6 +828,13 @@ class AnomalyDetector(Detector):
             return
         self.bank = ops.l2_normalize_rows(self._dev(bank))
 
+    def _quantise(self, rows) -> None:
+        """bank_dtype='int8': the 8-bit code of the fp32 rows -- lo / hi their smallest / largest element -- and the coded bank."""
+        lo, hi = torch.aminmax(rows)
+        lo, s, inv_s, _ = ops.int8_quantiser(lo.item(), hi.item())
+        self.bank, self.bank_sq, _ = ops.rows_to_int8(rows, lo, inv_s, s)
+        self.quant = (lo, s)
+
     def state(self):
         """What another rank needs to score like this detector (tools.inference under torch.distributed): the metric and the bank
         rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel.  With a
@@ -802,7 +842,9 @@ class AnomalyDetector(Detector):
         sorted by cell and the state also carries `perm`, `offsets`, `centroids`, `nlist` and `nprobe`."""
         state = {"metric": self.metric, "bank": self.bank.cpu()}
         if self.bank_dtype != 'float32':
-            state["bank_dtype"] = self.bank_dtype       # `bank` holds the rounded rows as torch.float16
+            state["bank_dtype"] = self.bank_dtype       # `bank` holds the rounded rows as torch.float16, or the codes as torch.int8
+        if self.bank_dtype == 'int8':
+            state.update(bank_sq=self.bank_sq.cpu(), lo=self.quant[0], s=self.quant[1])
         if self.gallery is not None:
             state["gallery"] = self.gallery
         if self.n_neighbors != 3:
@@ -828,6 +870,14 @@ class AnomalyDetector(Detector):
         if self.bank_dtype == 'float16':
             # the halves are fixed points of h, so rounding their fp32 values again returns them and the norms in the fit's order
             self.bank, self.bank_sq = ops.rows_to_half(self._dev(state["bank"]))
+            self.ivf = None
+            return
+        if self.bank_dtype == 'int8':
+            # the codes and their integer norms travel as they are: nothing is recomputed, so nothing can differ between ranks
+            dev = self._dev(torch.zeros(1)).device
+            self.bank = torch.as_tensor(state["bank"], dtype=torch.int8).to(dev).contiguous()
+            self.bank_sq = torch.as_tensor(state["bank_sq"], dtype=torch.int32).to(dev).contiguous()
+            self.quant = (float(state["lo"]), float(state["s"]))
             self.ivf = None
             return
         if self.gallery is not None:
@@ -863,6 +913,9 @@ class AnomalyDetector(Detector):
             if self.k > 3:
                 return ops.l2h_topk_mean(x, self.bank, self.bank_sq, self.k)
             return ops.l2h_knn_fused(x, self.bank, self.bank_sq, self.k)
+        if self.bank_dtype == 'int8':
+            self._check_width("predict", x.shape[1])
+            return ops.l2q_knn_fused(x, self.bank, self.bank_sq, self.quant, self.k)
         if self.gallery is not None:
             self._check_width("predict", x.shape[1])
             gallery, _ = self.retrieve(x)
@@ -903,6 +956,8 @@ class AnomalyDetector(Detector):
         k = self.k if k is None else int(k)
         if self.bank_dtype == 'float16':
             dist, idx = (ops.l2h_topk_index if k > 3 else ops.l2h_knn_index)(x, self.bank, self.bank_sq, k)
+        elif self.bank_dtype == 'int8':
+            dist, idx = ops.l2q_knn_index(x, self.bank, self.bank_sq, self.quant, k)
         elif self.gallery is not None:
             gallery, _ = self.retrieve(x)
             dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, k)
@@ -927,7 +982,7 @@ class AnomalyDetector(Detector):
 
     def _check_image_scores(self, mode, neighbours) -> None:
         check_image_scores(mode, neighbours, self.gallery, self.index)
-        check_bank_dtype(self.bank_dtype, self.metric, self.index, self.gallery, mode)
+        check_bank_dtype(self.bank_dtype, self.metric, self.index, self.gallery, mode, self.k)
         if not self.patch_level or not self.dim:
             raise ValueError("image_scores needs a patch-level detector (patch_level=True with num_patches)")
         if self.bank is None:

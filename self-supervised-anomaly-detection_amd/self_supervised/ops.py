@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI: allocate outputs with torch, launch on the current stream."""
 import os
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -983,6 +984,103 @@ def l2h_knn_index(x, bank_h, bank_sq, k=3, splits=None):
          lambda: _hip.lib().ssad_l2h_knn_index_split(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq),
                                                      _hip.ptr(part, dtype=torch.int64), _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d,
                                                      r, k, s, _hip.stream()))
+    return dist, idx
+
+
+INT8_MAX_D = 32768      # D 255^2 -- the largest squared code distance -- fits int32 up to here (csrc/knn_l2_int8.hip)
+
+
+def _int8_from_step(s):
+    """(s, inv_s, s2) from the fp32 step s: inv_s = 1 / s and s2 = s s in float64, each rounded once to fp32."""
+    s = float(np.float32(s))
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError(f"the int8 step must be finite and positive, got {s}")
+    return s, float(np.float32(1.0 / s)), float(np.float32(s * s))
+
+
+def int8_quantiser(lo, hi):
+    """The uniform 8-bit code of a bank whose smallest / largest element are lo / hi (faiss' QT_8bit_uniform): (lo, s, inv_s, s2) as
+    Python floats holding fp32 values -- lo as given (an fp32 value), s = (hi - lo) / 255 (1 when hi == lo) computed in float64 and
+    rounded once to fp32, inv_s = 1 / s and s2 = s s likewise from that s, so (lo, s) alone reproduce all four.  ValueError unless
+    both are finite."""
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"int8_quantiser: the bank's range must be finite, got [{lo}, {hi}]")
+    return (float(np.float32(lo)),) + _int8_from_step((hi - lo) / 255.0 if hi != lo else 1.0)
+
+
+def _check_int8_width(name, d):
+    if d % 32 or d > INT8_MAX_D:
+        raise ValueError(f"{name}: the int8 kernels need a width that is a multiple of 32 (at most {INT8_MAX_D}), got {d}")
+
+
+def rows_to_int8(x, lo, inv_s, s):
+    """x [N][D] fp32 -> (codes [N][D] int8, sq [N] int32, excess [N] float32) in one pass (csrc/knn_l2_int8.hip ssad_rows_to_int8):
+    the code rint(min(max((x - lo) * inv_s, 0), 255)) - 128 of every element (fp32, to nearest even, NaN -> -128), the sum of the
+    squared codes of every row, and excess = sum (x - clamp(x, lo, lo + 255 s))^2 in row_sqnorms' order -- what the clamp took from
+    the row: 0 inside the coded range.  (lo, s, inv_s): int8_quantiser."""
+    n, d = x.shape
+    _check_int8_width("rows_to_int8", d)
+    codes = torch.empty((n, d), device=x.device, dtype=torch.int8)
+    sq = torch.empty((n,), device=x.device, dtype=torch.int32)
+    excess = _new((n,), x)
+    _run("rows_to_int8", 4.0 * n * d, 5.0 * x.numel() + 8.0 * n,
+         lambda: _hip.lib().ssad_rows_to_int8(_hip.ptr(x), _hip.ptr(codes, dtype=torch.int8), _hip.ptr(sq, dtype=torch.int32),
+                                              _hip.ptr(excess), n, d, float(lo), float(inv_s), float(s), _hip.stream()))
+    return codes, sq, excess
+
+
+def _l2q_args(name, x, bank_q, bank_sq, quant, k, splits):
+    n, d = x.shape
+    r = bank_q.shape[0]
+    k = int(k)
+    _check_int8_width(name, d)
+    if bank_q.dtype != torch.int8 or bank_q.shape[1] != d or bank_sq.dtype != torch.int32 or bank_sq.shape[0] != r:
+        raise ValueError(f"{name}: the bank must be [R][{d}] int8 codes with their [R] int32 squared norms (rows_to_int8)")
+    if not 1 <= k <= 3:
+        raise ValueError(f"{name}: k must be 1, 2 or 3, got {k}")
+    if r < k:
+        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"{name}: splits must be >= 1, got {s}")
+    lo = float(np.float32(quant[0]))
+    if not np.isfinite(lo):
+        raise ValueError(f"{name}: quant = (lo, s) must be finite, got {tuple(quant)!r}")
+    return (n, d, r, k, s, lo) + _int8_from_step(quant[1])
+
+
+def l2q_knn_fused(x, bank_q, bank_sq, quant, k=3, splits=None):
+    """l2_knn_fused on an 8-bit scalar-quantised bank: x [N][D] fp32 queries (coded here, rows_to_int8, with the bank's code),
+    (bank_q, bank_sq, _) = rows_to_int8(bank, ...), quant = (lo, s) -> [N] mean of the k smallest distances BETWEEN THE CODES,
+    sqrt(s^2 D2 + excess(x)), D2 the exact int32 squared code distance on the int8 matrix cores (csrc/knn_l2_int8.hip
+    ssad_l2q_knn_fused).  `splits` as in l2_knn_fused; the same bits for every S."""
+    n, d, r, k, s, lo, step, inv_s, s2 = _l2q_args("l2q_knn_fused", x, bank_q, bank_sq, quant, k, splits)
+    xq, xsq, xex = rows_to_int8(x, lo, inv_s, step)
+    out = _new((n,), x)
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int32) if s > 1 else None     # squared code distances
+    i8, i32 = torch.int8, torch.int32
+    _run("l2q_knn_fused", 2.0 * n * d * r, 1.0 * (x.numel() + bank_q.numel()) + 4.0 * (r + 3 * n) + 8.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_l2q_knn_fused(_hip.ptr(xq, dtype=i8), _hip.ptr(xsq, dtype=i32), _hip.ptr(xex), _hip.ptr(bank_q, dtype=i8),
+                                               _hip.ptr(bank_sq, dtype=i32), _hip.ptr(part, True, i32), _hip.ptr(out), n, d, r, k, s, s2,
+                                               _hip.stream()))
+    return out
+
+
+def l2q_knn_index(x, bank_q, bank_sq, quant, k=3, splits=None):
+    """l2_knn_index on an 8-bit scalar-quantised bank (arguments as l2q_knn_fused): (dist [N][k] float32, idx [N][k] int32), the k
+    smallest (D2, bank row) pairs between the codes, equal D2 to the smaller row -- exactly the first k of a stable sort, the D2
+    being integers; dist holds the bits l2q_knn_fused averages (csrc/knn_l2_int8.hip ssad_l2q_knn_index)."""
+    n, d, r, k, s, lo, step, inv_s, s2 = _l2q_args("l2q_knn_index", x, bank_q, bank_sq, quant, k, splits)
+    xq, xsq, xex = rows_to_int8(x, lo, inv_s, step)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64) if s > 1 else None     # (D2 << 32 | row) keys
+    i8, i32 = torch.int8, torch.int32
+    _run("l2q_knn_index", 2.0 * n * d * r, 1.0 * (x.numel() + bank_q.numel()) + 4.0 * (r + 2 * n + 2 * n * k) + 16.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_l2q_knn_index(_hip.ptr(xq, dtype=i8), _hip.ptr(xsq, dtype=i32), _hip.ptr(xex), _hip.ptr(bank_q, dtype=i8),
+                                               _hip.ptr(bank_sq, dtype=i32), _hip.ptr(part, True, torch.int64), _hip.ptr(dist),
+                                               _hip.ptr(idx, dtype=i32), n, d, r, k, s, s2, _hip.stream()))
     return dist, idx
 
 

@@ -429,12 +429,13 @@ def _check_index(index, nlist, nprobe, index_options, detector, metric, gallery)
     return check_index(index, nlist, nprobe, index_options, metric, gallery)
 
 
-def _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores):
-    """The bank_dtype option of the kNN detector (models.check_bank_dtype; faiss' useFloat16): 'float16' = the flat Euclidean search
-    with operands rounded to fp16; either level, localization, dense_features and bank, with or without a coreset."""
+def _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores, n_neighbors=3):
+    """The bank_dtype option of the kNN detector (models.check_bank_dtype; faiss' useFloat16 and QT_8bit_uniform): 'float16' = the flat
+    Euclidean search with operands rounded to fp16, 'int8' = with an 8-bit scalar-quantised bank (n_neighbors 1..3); either level,
+    localization, dense_features and bank, with or without a coreset."""
     if bank_dtype != 'float32' and bank_dtype in models.BANK_DTYPES and detector != 'knn':
         raise ValueError(f"bank_dtype={bank_dtype!r} applies to detector='knn' only, got detector={detector!r}")
-    return check_bank_dtype(bank_dtype, metric, index, gallery, image_scores)
+    return check_bank_dtype(bank_dtype, metric, index, gallery, image_scores, n_neighbors)
 
 
 def _check_n_neighbors(n_neighbors, detector, metric, index, gallery):
@@ -537,7 +538,7 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
     _check_gallery(gallery, detector, metric, patch_localization, bank, coreset)
     _check_index(index, nlist, nprobe, index_options, detector, metric, gallery)
     _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery, index)
-    _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores)
+    _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores, n_neighbors)
     n_neighbors = _check_n_neighbors(n_neighbors, detector, metric, index, gallery)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
     if dense_features == 'pyramid' and detector == 'padim':
@@ -800,7 +801,10 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     (AnomalyDetector(bank_dtype='float16'); faiss' useFloat16): bank rows and queries ARE ROUNDED TO fp16, so the distances are those
     between the rounded rows; the bank takes half the memory, on every rank and in the broadcast.  Needs detector='knn',
     metric='euclidean', index='flat' and gallery=None; either level, localization, dense_features and bank, with or without a
-    coreset (selected on the fp32 rows); image_scores 'max' only.
+    coreset (selected on the fp32 rows); image_scores 'max' only.  'int8' = an 8-bit scalar-quantised bank
+    (AnomalyDetector(bank_dtype='int8'); faiss' QT_8bit_uniform): one affine code over the range of the bank rows that are kept, the
+    bank a quarter of the fp32 bytes, the distances THOSE BETWEEN THE CODES (plus what the clamp to the bank's range took from a
+    query), within s sqrt(D) of the fp32 ones for queries inside that range (s = range / 255).  Same conditions, and n_neighbors 1..3.
     `n_neighbors`: the k of the kNN score (AnomalyDetector(n_neighbors=k); sklearn's n_neighbors, PatchCore's anomaly_scorer_num_nn,
     SPADE's kappa), default 3 as the reference: maps, threshold and the patch scores under `image_scores` are the mean distance to
     the k nearest bank rows.  1..3 on every path; 4..32 need metric='euclidean', index='flat' and gallery=None (either bank_dtype).
