@@ -65,8 +65,8 @@ class Detector:
         """``fit``'s refusals, before the split is drawn; returns the groups it is drawn over."""
         return groups
 
-    def _after_bank(self) -> None:
-        """Between ``fit_bank`` and the threshold."""
+    def _after_bank(self, train) -> None:
+        """Between ``fit_bank`` and the threshold.  train: the rows ``fit_bank`` was given."""
 
     def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
         """Fits on 70 % of the rows, `threshold` = the largest score of the other 30 % (split=False: both on every row).  groups: image
@@ -77,7 +77,7 @@ class Detector:
             train_idx, val_idx = split_rows(int(emb.shape[0]), groups, 0.3)
             train, val = _take(emb, train_idx), _take(emb, val_idx)
         self.fit_bank(train)
-        self._after_bank()
+        self._after_bank(train)
         self.threshold = torch.max(self._scores(self._dev(val))).item()
 
     def predict(self, x: Tensor) -> Tensor:

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import engine, ops
+from . import engine, knn_search, ops
 from .constants import ModelOutputsContainer
 from .converters import gt2label, multiclass2binary
 from .density import GaussianDensityDetector, PositionGaussianDetector  # noqa: F401  (re-exported)
@@ -638,7 +638,8 @@ class AnomalyDetector(Detector):
     """src/self_supervised/models.py:345-370: cosine 3-NN distance to a bank of normal embeddings.
 
     ``fit`` keeps the reference's unseeded 70/30 split (quirk Q5: depends on the global numpy RNG);
-    the bank is L2-normalised once and kept on the GPU, ``predict`` = normalise + MFMA GEMM + top-3 mean.
+    the bank is L2-normalised once and kept on the GPU, ``predict`` = normalise + MFMA GEMM + top-3 mean.  The options below choose
+    one of six ways to keep and search the bank; each is one class of knn_search.py, picked once by the constructor.
 
     `coreset` (opt-in; the reference keeps every row): None = the exact bank; a fraction f in (0, 1] or an int m >= 1 = ``fit`` keeps
     m = ceil(f R) (or m) of the R bank rows left after the split, chosen by a greedy k-center selection (coreset_select) on the
@@ -715,9 +716,10 @@ class AnomalyDetector(Detector):
         self.ivf = None                 # index='ivf' after fit: perm, offsets, centroids, cent_sq, nlist, nprobe (bank: sorted by cell)
         self.bank_dtype = check_bank_dtype(bank_dtype, self.metric, self.index, self.gallery, None, n_neighbors)
         self.k = check_n_neighbors(n_neighbors, self.metric, self.index, self.gallery)      # the one place n_neighbors is kept
-        self._rows32 = None            # bank_dtype='float16' / 'int8', inside fit with a coreset: the fp32 rows the selection runs on
         if self.bank_dtype == 'int8':
             self.quant = None           # after fit: (lo, s) of the bank's 8-bit code (ops.int8_quantiser)
+        # how the bank is kept and searched: everything below delegates to it (knn_search.py); the data stays in the attributes above
+        self._search = knn_search.choose(self.metric, self.index, self.gallery, self.bank_dtype)
 
     @property
     def n_neighbors(self) -> int:
@@ -746,42 +748,17 @@ class AnomalyDetector(Detector):
             raise ValueError(f"fit: with a gallery, every image must have exactly num_patches = {self.patches} contiguous rows")
         return groups
 
-    def _after_bank(self) -> None:
-        self.k = self.n_neighbors       # as the reference's fit sets it (the literal 3 there); read by _scores for the threshold
-        if self.gallery is not None:
-            self.bank_desc = ops.group_means(self.bank, self.patches)
+    def _after_bank(self, train) -> None:
         if self.coreset is not None:
             r = int(self.bank.shape[0])
             m = coreset_size(self.coreset, r)
             if m < r:
-                sel, rad = coreset_select(self.bank if self._rows32 is None else self._rows32, m, self.coreset_dim)
-                if self.bank_dtype == 'int8':
-                    self._quantise(self._rows32.index_select(0, sel).contiguous())     # the code spans the rows that are kept
-                else:
-                    self.bank = self.bank.index_select(0, sel).contiguous()
-                    if self.bank_sq is not None:
-                        self.bank_sq = self.bank_sq.index_select(0, sel).contiguous()
+                rows = self._search.coreset_rows(self, train)       # fp32: the bank, or `train` again where the bank is fp16 / int8
+                sel, rad = coreset_select(rows, m, self.coreset_dim)
+                self._search.keep(self, sel, rows)
                 self.coreset_rows = (sel, rad)
             self.coreset_counts = (int(self.bank.shape[0]), r)
-        if self.index == 'ivf':
-            self._build_index()
-
-    def _build_index(self) -> None:
-        """Clusters the bank rows and re-stores them cell after cell (stable in the caller's row order within a cell)."""
-        r = int(self.bank.shape[0])
-        nlist = ivf_nlist(self.nlist, r)
-        centroids, assign = ops.kmeans_l2(self.bank, nlist, **self.index_options)
-        sorted_cells, perm = torch.sort(assign, stable=True)
-        self.bank = self.bank.index_select(0, perm).contiguous()
-        self.bank_sq = ops.row_sqnorms(self.bank)
-        self._set_index(perm.to(torch.int32), ops.cell_offsets(sorted_cells, nlist), centroids, nlist, min(self.nprobe, nlist))
-
-    def _set_index(self, perm, offsets, centroids, nlist, nprobe) -> None:
-        self.ivf = {"perm": perm.contiguous(), "offsets": offsets.contiguous(), "centroids": centroids.contiguous(),
-                    "cent_sq": ops.row_sqnorms(centroids), "nlist": int(nlist), "nprobe": int(nprobe)}
-
-    def _probes(self, x):
-        return ops.ivf_probes(x, self.ivf["centroids"], self.ivf["cent_sq"], self.ivf["nprobe"])
+        self._search.finish(self)
 
     def describe_fit(self):
         lines = [] if self.coreset_counts is None else [f' coreset: {self.coreset_counts[0]} of {self.coreset_counts[1]} rows']
@@ -791,70 +768,18 @@ class AnomalyDetector(Detector):
                          f'{int(np.median(sizes))} / {int(sizes.max())} rows (smallest / median / largest), {int((sizes == 0).sum())} empty')
         return '\n'.join(lines) if lines else None
 
-    def _check_width(self, what, d):
-        if d % 32:
-            raise ValueError(f"{what}: metric='euclidean' needs an embedding width that is a multiple of 32, got {d}")
-
-    def fit(self, embeddings: Tensor, split: bool = True, groups=None) -> None:
-        if self.bank_dtype == 'float32' or self.coreset is None:
-            return super().fit(embeddings, split, groups)
-        self._rows32 = True             # fit_bank keeps the fp32 rows for the coreset selection of _after_bank
-        try:
-            super().fit(embeddings, split, groups)
-        finally:
-            self._rows32 = None
-
     def fit_bank(self, bank: Tensor) -> None:
         self.ivf = None                 # the rows as given: an index is built by fit (_after_bank) or arrives with load_state
-        if self.bank_dtype == 'float16':
-            self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
-            rows = self._dev(bank)
-            self.bank, self.bank_sq = ops.rows_to_half(rows)
-            self._rows32 = rows if self._rows32 is not None else None
-            return
-        if self.bank_dtype == 'int8':
-            self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
-            rows = self._dev(bank)
-            self._quantise(rows)
-            self._rows32 = rows if self._rows32 is not None else None
-            return
-        if self.metric == 'euclidean':
-            self._check_width("fit_bank", int(torch.as_tensor(bank).shape[1]))
-            if self.gallery is not None:
-                self._whole_images("fit_bank", int(torch.as_tensor(bank).shape[0]))
-                self.bank_desc = None
-            self.bank = self._dev(bank)
-            self.bank_sq = ops.row_sqnorms(self.bank)
-            return
-        self.bank = ops.l2_normalize_rows(self._dev(bank))
-
-    def _quantise(self, rows) -> None:
-        """bank_dtype='int8': the 8-bit code of the fp32 rows -- lo / hi their smallest / largest element -- and the coded bank."""
-        lo, hi = torch.aminmax(rows)
-        lo, s, inv_s, _ = ops.int8_quantiser(lo.item(), hi.item())
-        self.bank, self.bank_sq, _ = ops.rows_to_int8(rows, lo, inv_s, s)
-        self.quant = (lo, s)
+        self._search.store(self, bank)
 
     def state(self):
         """What another rank needs to score like this detector (tools.inference under torch.distributed): the metric and the bank
-        rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel.  With a
-        gallery the state names it (`gallery`: K); `bank_desc` is recomputed like `bank_sq`.  With index='ivf' `bank` is the bank
-        sorted by cell and the state also carries `perm`, `offsets`, `centroids`, `nlist` and `nprobe`."""
-        state = {"metric": self.metric, "bank": self.bank.cpu()}
-        if self.bank_dtype != 'float32':
-            state["bank_dtype"] = self.bank_dtype       # `bank` holds the rounded rows as torch.float16, or the codes as torch.int8
-        if self.bank_dtype == 'int8':
-            state.update(bank_sq=self.bank_sq.cpu(), lo=self.quant[0], s=self.quant[1])
-        if self.gallery is not None:
-            state["gallery"] = self.gallery
-        if self.n_neighbors != 3:
-            state["n_neighbors"] = self.n_neighbors     # absent = 3: states written before the option still load
-        if self.index == 'ivf':
-            if self.ivf is None:
-                raise ValueError("state: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
-            state.update({k: self.ivf[k].cpu() for k in ("perm", "offsets", "centroids")}, nlist=self.ivf["nlist"],
-                         nprobe=self.ivf["nprobe"])
-        return state
+        rows as they are kept, on the host.  `bank_sq` does not travel: load_state recomputes it with the same kernel.  With
+        bank_dtype 'float16' or 'int8' the state names it (`bank_dtype`) and `bank` holds the halves or the codes; 'int8' also
+        carries `bank_sq`, `lo` and `s`.  With a gallery the state names it (`gallery`: K); `bank_desc` is recomputed like `bank_sq`.
+        With index='ivf' `bank` is the bank sorted by cell and the state also carries `perm`, `offsets`, `centroids`, `nlist` and
+        `nprobe`.  `n_neighbors` travels unless it is 3."""
+        return self._search.state(self)
 
     def load_state(self, state) -> None:
         if state["metric"] != self.metric:
@@ -867,79 +792,20 @@ class AnomalyDetector(Detector):
         if state.get("n_neighbors", 3) != self.n_neighbors:
             raise ValueError(f"load_state: the bank was fitted with n_neighbors={state.get('n_neighbors', 3)!r}, this detector has "
                              f"{self.n_neighbors!r}")
-        if self.bank_dtype == 'float16':
-            # the halves are fixed points of h, so rounding their fp32 values again returns them and the norms in the fit's order
-            self.bank, self.bank_sq = ops.rows_to_half(self._dev(state["bank"]))
-            self.ivf = None
-            return
-        if self.bank_dtype == 'int8':
-            # the codes and their integer norms travel as they are: nothing is recomputed, so nothing can differ between ranks
-            dev = self._dev(torch.zeros(1)).device
-            self.bank = torch.as_tensor(state["bank"], dtype=torch.int8).to(dev).contiguous()
-            self.bank_sq = torch.as_tensor(state["bank_sq"], dtype=torch.int32).to(dev).contiguous()
-            self.quant = (float(state["lo"]), float(state["s"]))
-            self.ivf = None
-            return
-        if self.gallery is not None:
-            self._whole_images("load_state", int(state["bank"].shape[0]))
-        self.bank = self._dev(state["bank"])
-        self.bank_sq = ops.row_sqnorms(self.bank) if self.metric == 'euclidean' else None
-        self.bank_desc = ops.group_means(self.bank, self.patches) if self.gallery is not None else None
         if ("nlist" in state) != (self.index == 'ivf'):
             raise ValueError(f"load_state: the bank was fitted with index={'ivf' if 'nlist' in state else 'flat'!r}, this detector has "
                              f"{self.index!r}")
         self.ivf = None
-        if self.index == 'ivf':
-            dev = self.bank.device
-            self._set_index(state["perm"].to(dev), state["offsets"].to(dev), state["centroids"].to(dev), state["nlist"], state["nprobe"])
+        self._search.load(self, state)
 
     def retrieve(self, x):
         """Stage 1 of the gallery for the whole query images x [Q * num_patches][D] (on the device): (gallery int32 [Q][K'],
         d2 float32 [Q][K']), the K' = min(K, T) bank images nearest to each query image by the squared distance between the image
         descriptors, nearest first, equal distances to the smaller image, and those squared distances."""
-        if self.gallery is None:
-            raise ValueError("retrieve: the detector has no gallery (AnomalyDetector(gallery=K))")
-        self._whole_images("predict", int(x.shape[0]))
-        if self.bank_desc is None:
-            self.bank_desc = ops.group_means(self.bank, self.patches)
-        d2 = ops.l2_direct(ops.group_means(x, self.patches), self.bank_desc)
-        vals, order = torch.sort(d2, dim=1, stable=True)
-        kq = min(self.gallery, int(d2.shape[1]))
-        return order[:, :kq].to(torch.int32).contiguous(), vals[:, :kq].contiguous()
+        return self._search.retrieve(self, x)
 
     def _scores(self, x):
-        if self.bank_dtype == 'float16':
-            self._check_width("predict", x.shape[1])
-            if self.k > 3:
-                return ops.l2h_topk_mean(x, self.bank, self.bank_sq, self.k)
-            return ops.l2h_knn_fused(x, self.bank, self.bank_sq, self.k)
-        if self.bank_dtype == 'int8':
-            self._check_width("predict", x.shape[1])
-            return ops.l2q_knn_fused(x, self.bank, self.bank_sq, self.quant, self.k)
-        if self.gallery is not None:
-            self._check_width("predict", x.shape[1])
-            gallery, _ = self.retrieve(x)
-            return ops.l2_knn_gallery(x, self.bank, self.bank_sq, gallery, self.patches, self.k)
-        if self.index == 'ivf':
-            self._check_width("predict", x.shape[1])
-            if self.ivf is None:
-                raise ValueError("predict: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
-            return ops.l2_knn_ivf(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"], self.k)
-        if self.metric == 'euclidean':
-            self._check_width("predict", x.shape[1])
-            if self.k > 3:
-                return ops.l2_topk_mean(x, self.bank, self.bank_sq, self.k)
-            return ops.l2_knn_fused(x, self.bank, self.bank_sq, self.k)
-        if x.shape[1] % 32 == 0 and 1 <= self.k <= 3:
-            # normalise + similarity GEMM + k smallest distances in one kernel: no N x bank matrix in HBM (csrc/knn.hip)
-            return ops.cosine_knn_fused(x, self.bank, self.k)
-        qn = ops.l2_normalize_rows(x)
-        out = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
-        step = 1 << 18
-        for i in range(0, x.shape[0], step):
-            sim = ops.linear_fwd(qn[i:i + step], self.bank)
-            out[i:i + step] = ops.cosine_knn_mean(sim, self.k)
-        return out
+        return self._search.scores(self, x)
 
     def kneighbors(self, x: Tensor, k: int = None):
         """sklearn's NearestNeighbors.kneighbors (what the reference's detector wraps) on the fitted bank: (dist [N][k] float32,
@@ -953,22 +819,7 @@ class AnomalyDetector(Detector):
         x = self._dev(x)
         if x.shape[1] % 32:
             raise ValueError(f"kneighbors: the index kernel needs an embedding width that is a multiple of 32, got {x.shape[1]}")
-        k = self.k if k is None else int(k)
-        if self.bank_dtype == 'float16':
-            dist, idx = (ops.l2h_topk_index if k > 3 else ops.l2h_knn_index)(x, self.bank, self.bank_sq, k)
-        elif self.bank_dtype == 'int8':
-            dist, idx = ops.l2q_knn_index(x, self.bank, self.bank_sq, self.quant, k)
-        elif self.gallery is not None:
-            gallery, _ = self.retrieve(x)
-            dist, idx = ops.l2_knn_gallery_index(x, self.bank, self.bank_sq, gallery, self.patches, k)
-        elif self.index == 'ivf':
-            if self.ivf is None:
-                raise ValueError("kneighbors: index='ivf' has no index yet (fit first; fit_bank alone builds none)")
-            dist, idx = ops.l2_knn_ivf_index(x, self.bank, self.bank_sq, self.ivf["offsets"], self._probes(x), self.ivf["perm"], k)
-        elif self.metric == 'euclidean':
-            dist, idx = (ops.l2_topk_index if k > 3 else ops.l2_knn_index)(x, self.bank, self.bank_sq, k)
-        else:
-            dist, idx = ops.cosine_knn_index(x, self.bank, k)
+        dist, idx = self._search.kneighbors(self, x, self.k if k is None else int(k))
         return dist, idx.long()
 
     def image_scores(self, x: Tensor, mode: str = 'max', neighbours: int = 9, scores: Tensor = None) -> Tensor:
@@ -996,18 +847,7 @@ class AnomalyDetector(Detector):
     def _reweight(self, xs, smax, neighbours):
         """image_scores(mode='reweighted') (PatchCore eq. 6-7 with the detector's metric): w s_{p*}, w = 1 - exp(d(x_{p*}, m*)) /
         sum_{r in N} exp(d(x_{p*}, r)), m* the nearest bank row of x_{p*} (`xs`), N the min(neighbours, R) bank rows nearest to B_{m*}."""
-        if self.metric == 'euclidean':
-            _, mstar = ops.l2_knn_index(xs, self.bank, self.bank_sq, 1)
-            rows = mstar.reshape(-1).long()
-            dots = ops.linear_fwd(self.bank.index_select(0, rows), self.bank)                    # <B_{m*}, B_r>
-            d2 = ops.l2_from_dots(dots, self.bank_sq.index_select(0, rows), self.bank_sq)
-            _, nbr = ops.rows_smallest_index(d2, neighbours, cosine=False)
-            return ops.knn_reweight_l2(xs, self.bank, mstar, nbr, smax)
-        _, mstar = ops.cosine_knn_index(xs, self.bank, 1)                # m*: an index pass over one row per image
-        centre = self.bank.index_select(0, mstar.reshape(-1).long())     # B_{m*}
-        sim = ops.linear_fwd(centre, self.bank)                          # [batch][R] similarities of B_{m*} to the bank
-        _, nbr = ops.rows_smallest_index(sim, neighbours, cosine=True)   # N: the rows nearest to B_{m*}
-        return ops.knn_reweight(xs, self.bank, mstar, nbr, smax)
+        return self._search.reweight(self, xs, smax, neighbours)
 
 
 DETECTORS = {'knn': AnomalyDetector, 'gde': GaussianDensityDetector, 'padim': PositionGaussianDetector}     # tools.inference(detector=...)

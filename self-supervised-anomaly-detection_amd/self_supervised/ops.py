@@ -859,19 +859,40 @@ def _check_l2_width(name, d):
         raise ValueError(f"{name}: the Euclidean kernels need a width that is a multiple of 32 (at most 65536), got {d}")
 
 
+# bank dtype of a flat Euclidean search -> (dtype of bank_sq, what the two hold and the op that makes them)
+_L2_BANKS = {torch.float32: (torch.float32, "float32 rows with their [R] float32 squared norms (row_sqnorms)"),
+             torch.float16: (torch.float32, "float16 rows with their [R] float32 squared norms (rows_to_half)"),
+             torch.int8: (torch.int32, "int8 codes with their [R] int32 squared norms (rows_to_int8)")}
+
+
+def _l2_flat_args(name, x, bank, bank_sq, k, splits, bank_dtype, k_range=(1, 3)):
+    """The argument checks of every flat Euclidean search (fp32, fp16 and int8 banks, k <= 3 and the list kernels), from shapes and
+    dtypes alone, so before any launch: the width, the bank of `bank_dtype` with one squared norm per row, k within `k_range` and at
+    most the bank's rows, `splits` None (the knn_splits rule) or >= 1.  -> (n, d, r, k, s)."""
+    n, d = x.shape
+    r = bank.shape[0]
+    k = int(k)
+    _check_l2_width(name, d)
+    sq_dtype, holds = _L2_BANKS[bank_dtype]
+    if bank.dtype != bank_dtype or bank.shape[1] != d or bank_sq.dtype != sq_dtype or tuple(bank_sq.shape) != (r,):
+        raise ValueError(f"{name}: the bank must be [R][{d}] {holds}, got {bank.dtype} {tuple(bank.shape)} and {bank_sq.dtype} "
+                         f"{tuple(bank_sq.shape)}")
+    if not k_range[0] <= k <= k_range[1]:
+        allowed = "be 1, 2 or 3" if k_range == (1, 3) else f"lie in {k_range[0]}..{k_range[1]} (1..3: the l2_knn / l2h_knn functions)"
+        raise ValueError(f"{name}: k must {allowed}, got {k}")
+    if r < k:
+        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
+    s = knn_splits(n, r) if splits is None else int(splits)
+    if s < 1:
+        raise ValueError(f"{name}: splits must be >= 1, got {s}")
+    return n, d, r, k, s
+
+
 def l2_knn_fused(x, bank, bank_sq, k=3, splits=None):
     """x [N][D], bank [R][D] (neither normalised), bank_sq = row_sqnorms(bank) -> [N] mean of the k smallest Euclidean distances
     sqrt(max(|x|^2 + |b|^2 - 2 <x, b>, 0)) (csrc/knn_l2.hip ssad_l2_knn_fused / _split).  `splits`: None = the knn_splits rule; S >= 1 =
     that many bank splits (1: one launch); the same bits for every S."""
-    n, d = x.shape
-    r = bank.shape[0]
-    k = int(k)
-    _check_l2_width("l2_knn_fused", d)
-    if not 1 <= k <= 3 or r < k:
-        raise ValueError(f"l2_knn_fused: k must be 1, 2 or 3 and at most the {r} bank rows, got {k}")
-    s = knn_splits(n, r) if splits is None else int(splits)
-    if s < 1:
-        raise ValueError(f"l2_knn_fused: splits must be >= 1, got {s}")
+    n, d, r, k, s = _l2_flat_args("l2_knn_fused", x, bank, bank_sq, k, splits, torch.float32)
     out = _new((n,), x)
     if s == 1:
         _run("l2_knn_fused", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n),
@@ -889,17 +910,7 @@ def l2_knn_index(x, bank, bank_sq, k=3, splits=None):
     """kneighbors of the Euclidean bank: (dist [N][k] float32, idx [N][k] int32), the k (1..3) smallest (squared distance, bank row)
     pairs of every query, ascending, equal ones to the smaller row; dist holds the roots -- the bits l2_knn_fused averages
     (csrc/knn_l2.hip ssad_l2_knn_index / _split).  `splits` as in l2_knn_fused."""
-    n, d = x.shape
-    r = bank.shape[0]
-    k = int(k)
-    _check_l2_width("l2_knn_index", d)
-    if not 1 <= k <= 3:
-        raise ValueError(f"l2_knn_index: k must be 1, 2 or 3, got {k}")
-    if r < k:
-        raise ValueError(f"l2_knn_index: the bank has {r} rows, fewer than k = {k}")
-    s = knn_splits(n, r) if splits is None else int(splits)
-    if s < 1:
-        raise ValueError(f"l2_knn_index: splits must be >= 1, got {s}")
+    n, d, r, k, s = _l2_flat_args("l2_knn_index", x, bank, bank_sq, k, splits, torch.float32)
     dist = _new((n, k), x)
     idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
     i32 = torch.int32
@@ -928,29 +939,12 @@ def rows_to_half(x):
     return xh, sq
 
 
-def _l2h_args(name, x, bank_h, bank_sq, k, splits):
-    n, d = x.shape
-    r = bank_h.shape[0]
-    k = int(k)
-    _check_l2_width(name, d)
-    if bank_h.dtype != torch.float16 or bank_h.shape[1] != d or bank_sq.shape[0] != r:
-        raise ValueError(f"{name}: the bank must be [R][{d}] float16 rows with their [R] squared norms (rows_to_half)")
-    if not 1 <= k <= 3:
-        raise ValueError(f"{name}: k must be 1, 2 or 3, got {k}")
-    if r < k:
-        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
-    s = knn_splits(n, r) if splits is None else int(splits)
-    if s < 1:
-        raise ValueError(f"{name}: splits must be >= 1, got {s}")
-    return n, d, r, k, s
-
-
 def l2h_knn_fused(x, bank_h, bank_sq, k=3, splits=None):
     """l2_knn_fused with half-precision operands: x [N][D] fp32 queries (rounded here, rows_to_half), (bank_h, bank_sq) =
     rows_to_half(bank) -> [N] mean of the k smallest distances BETWEEN THE ROUNDED ROWS, sqrt(max(|h(x)|^2 + |h(b)|^2 - 2 <h(x), h(b)>,
     0)), on the fp16 matrix cores (csrc/knn_l2_half.hip ssad_l2h_knn_fused / _split).  `splits` as in l2_knn_fused; the same bits for
     every S."""
-    n, d, r, k, s = _l2h_args("l2h_knn_fused", x, bank_h, bank_sq, k, splits)
+    n, d, r, k, s = _l2_flat_args("l2h_knn_fused", x, bank_h, bank_sq, k, splits, torch.float16)
     xh, xsq = rows_to_half(x)
     out = _new((n,), x)
     if s == 1:
@@ -969,7 +963,7 @@ def l2h_knn_index(x, bank_h, bank_sq, k=3, splits=None):
     """l2_knn_index with half-precision operands (arguments as l2h_knn_fused): (dist [N][k] float32, idx [N][k] int32), the k smallest
     (squared distance, bank row) pairs between the rounded rows, equal ones to the smaller row; dist holds the bits l2h_knn_fused
     averages (csrc/knn_l2_half.hip ssad_l2h_knn_index / _split)."""
-    n, d, r, k, s = _l2h_args("l2h_knn_index", x, bank_h, bank_sq, k, splits)
+    n, d, r, k, s = _l2_flat_args("l2h_knn_index", x, bank_h, bank_sq, k, splits, torch.float16)
     xh, xsq = rows_to_half(x)
     dist = _new((n, k), x)
     idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
@@ -1031,23 +1025,12 @@ def rows_to_int8(x, lo, inv_s, s):
 
 
 def _l2q_args(name, x, bank_q, bank_sq, quant, k, splits):
-    n, d = x.shape
-    r = bank_q.shape[0]
-    k = int(k)
-    _check_int8_width(name, d)
-    if bank_q.dtype != torch.int8 or bank_q.shape[1] != d or bank_sq.dtype != torch.int32 or bank_sq.shape[0] != r:
-        raise ValueError(f"{name}: the bank must be [R][{d}] int8 codes with their [R] int32 squared norms (rows_to_int8)")
-    if not 1 <= k <= 3:
-        raise ValueError(f"{name}: k must be 1, 2 or 3, got {k}")
-    if r < k:
-        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
-    s = knn_splits(n, r) if splits is None else int(splits)
-    if s < 1:
-        raise ValueError(f"{name}: splits must be >= 1, got {s}")
+    _check_int8_width(name, x.shape[1])
+    args = _l2_flat_args(name, x, bank_q, bank_sq, k, splits, torch.int8)
     lo = float(np.float32(quant[0]))
     if not np.isfinite(lo):
         raise ValueError(f"{name}: quant = (lo, s) must be finite, got {tuple(quant)!r}")
-    return (n, d, r, k, s, lo) + _int8_from_step(quant[1])
+    return args + (lo,) + _int8_from_step(quant[1])
 
 
 def l2q_knn_fused(x, bank_q, bank_sq, quant, k=3, splits=None):
@@ -1088,22 +1071,7 @@ TOPK_MIN, TOPK_MAX = 4, 32     # k of the list kernels (csrc/knn_topk.hip); 1..3
 
 
 def _topk_args(name, x, bank, bank_sq, k, splits, half):
-    n, d = x.shape
-    r = bank.shape[0]
-    k = int(k)
-    _check_l2_width(name, d)
-    if half and bank.dtype != torch.float16:
-        raise ValueError(f"{name}: the bank must be [R][{d}] float16 rows with their [R] squared norms (rows_to_half)")
-    if bank.shape[1] != d or bank_sq.shape[0] != r:
-        raise ValueError(f"{name}: the bank must be [R][{d}] rows with their [R] squared norms, got {tuple(bank.shape)} and "
-                         f"{tuple(bank_sq.shape)}")
-    if not TOPK_MIN <= k <= TOPK_MAX:
-        raise ValueError(f"{name}: k must lie in {TOPK_MIN}..{TOPK_MAX} (1..3: the l2_knn / l2h_knn functions), got {k}")
-    if r < k:
-        raise ValueError(f"{name}: the bank has {r} rows, fewer than k = {k}")
-    s = knn_splits(n, r) if splits is None else int(splits)
-    if s < 1:
-        raise ValueError(f"{name}: splits must be >= 1, got {s}")
+    n, d, r, k, s = _l2_flat_args(name, x, bank, bank_sq, k, splits, torch.float16 if half else torch.float32, (TOPK_MIN, TOPK_MAX))
     part = torch.empty((s, n, k), device=x.device, dtype=torch.int64) if s > 1 else None   # (squared-distance bits << 32 | row) keys
     return n, d, r, k, s, part
 

@@ -26,6 +26,7 @@ import coreset_ref
 import knn_l2_half_ref as href
 import knn_l2_ref as ref
 from fake_mvtec import make_tree
+from knn_paths_util import fp32_rows_held
 
 pytestmark = pytest.mark.gpu
 
@@ -462,7 +463,7 @@ def test_detector_against_float64(coreset):
         want_sel, _ = coreset_ref.greedy64(proj.double().numpy(), m)
         assert np.array_equal(sel.cpu().numpy(), want_sel)
         rows = rows[sel.cpu()]
-    assert det.bank.dtype == torch.float16 and det._rows32 is None                  # the fp32 rows are gone
+    assert det.bank.dtype == torch.float16 and fp32_rows_held(det) == []                  # the fp32 rows are gone
     assert np.array_equal(half_bits(det.bank), href.h(rows).view(np.uint16)) and det.bank_sq.shape == (rows.shape[0],)
     assert torch.equal(det.bank_sq, ops.rows_to_half(rows.cuda())[1])
     x = gauss(200, 64, seed=9) * 0.5 + gauss(1, 64, seed=4)
@@ -526,7 +527,7 @@ def test_inference_half_bank(tmp_path, seeded_sd, monkeypatch, localization):
     assert seen["det"].bank.dtype == torch.float32
     res = run(bank_dtype='float16')
     det, rows32 = seen["det"], seen["rows32"]
-    assert det.bank_dtype == 'float16' and det.bank.dtype == torch.float16 and det._rows32 is None
+    assert det.bank_dtype == 'float16' and det.bank.dtype == torch.float16 and fp32_rows_held(det) == []
     assert np.array_equal(half_bits(det.bank), href.h(rows32).view(np.uint16))     # the fit rows, rounded
     assert torch.equal(det.bank_sq, ops.rows_to_half(rows32.cuda())[1])
     rows = res.embedding_vectors.float()

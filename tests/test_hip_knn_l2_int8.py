@@ -19,6 +19,7 @@ import torch
 import coreset_ref
 import knn_l2_int8_ref as qref
 from fake_mvtec import make_tree
+from knn_paths_util import fp32_rows_held
 
 pytestmark = pytest.mark.gpu
 
@@ -378,7 +379,7 @@ def test_detector_against_the_reference(coreset, patch_level):
         rows = rows[sel.cpu()]
     quant = qref.quantiser_of(rows)                                                 # lo / hi of the rows that are kept
     lo, s, inv_s, s2 = quant
-    assert det.quant == (float(lo), float(s)) and det._rows32 is None
+    assert det.quant == (float(lo), float(s)) and fp32_rows_held(det) == []
     assert det.bank.dtype == torch.int8 and det.bank_sq.dtype == torch.int32
     bc = qref.codes(rows, lo, inv_s)
     assert np.array_equal(det.bank.cpu().numpy(), bc) and np.array_equal(det.bank_sq.cpu().numpy().astype(np.int64), qref.sq64(bc))
@@ -499,7 +500,7 @@ def test_inference_int8_bank_equals_the_detector_called_by_hand(tmp_path, seeded
     assert seen["det"].bank.dtype == torch.float32
     res = run(bank_dtype='int8')
     det, rows32 = seen["det"], seen["rows32"]
-    assert det.bank_dtype == 'int8' and det.bank.dtype == torch.int8 and det._rows32 is None
+    assert det.bank_dtype == 'int8' and det.bank.dtype == torch.int8 and fp32_rows_held(det) == []
     rows = res.embedding_vectors.float()
     assert torch.equal(rows, before.embedding_vectors.float()) and rows.shape[1] % 32 == 0
     hand = AnomalyDetector(metric='euclidean', bank_dtype='int8')

@@ -155,9 +155,9 @@ def test_default_bank_dtype_leaves_the_detector_as_it_was():
     from self_supervised.models import AnomalyDetector
     for kw in ({}, {"metric": 'euclidean', "coreset": 0.5}, {"patch_level": True, "batch": 2, "num_patches": 25}):
         a, b = vars(AnomalyDetector(**kw)), vars(AnomalyDetector(bank_dtype='float32', **kw))
-        assert a == b and a["bank_dtype"] == 'float32' and a["_rows32"] is None
+        assert a == b and a["bank_dtype"] == 'float32'
     plain = vars(AnomalyDetector())
-    assert {k: plain[k] for k in TODAY} == TODAY and set(plain) - set(TODAY) == {"bank_dtype", "_rows32"}
+    assert {k: plain[k] for k in TODAY} == TODAY and set(plain) - set(TODAY) == {"bank_dtype", "_search"}     # (_search: no data)
     cls, kw = tools._check_options('knn', 'euclidean', 'patches', True, 'train', True, None, None, 9, None)
     assert "bank_dtype" not in kw
     cls, kw = tools._check_options('knn', 'euclidean', 'dense', True, 'train', True, 0.1, 'max', 9, None, bank_dtype='float16')
