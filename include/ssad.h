@@ -513,13 +513,11 @@ int ssad_cosine_knn_split(const float* x, const float* bank_normalized, float* p
  * returns (distances, indices); the two entries above keep the distances only).  Adds WHICH bank rows are the nearest: for every query
  * the k (1..3) smallest (distance, bank row) pairs in lexicographic order, ascending -- dist [N][k] float32, idx [N][k] int32; equal
  * distances go to the smaller row.  Tile, K order and distance expression of ssad_cosine_knn_fused: the distances are the bits it
- * averages.  ssad_cosine_knn_index: one launch.  ssad_cosine_knn_index_split: the bank split of ssad_cosine_knn_split, part [S][N][3]
- * 64-bit keys (caller-owned, 8-byte aligned; not read for S = 1) + a merge launch.  No atomics; dist and idx are the same bits for
- * every S and on every call.  D % 32 == 0, D <= 65536, k <= R, 1 <= S <= 65535. */
-int ssad_cosine_knn_index(const float* x, const float* bank_normalized, float* dist, int* idx, int64_t N, int D, int R, int k,
-                          void* stream);
-int ssad_cosine_knn_index_split(const float* x, const float* bank_normalized, void* part, float* dist, int* idx, int64_t N, int D, int R,
-                                int k, int S, void* stream);
+ * averages.  S bank splits: 1 = one launch (part unused, may be null); S > 1 = the bank split of ssad_cosine_knn_split, part [S][N][3]
+ * 64-bit keys (caller-owned, 8-byte aligned) + a merge launch.  No atomics; dist and idx are the same bits for every S and on every
+ * call.  D % 32 == 0, D <= 65536, k <= R, 1 <= S <= 65535. */
+int ssad_cosine_knn_index(const float* x, const float* bank_normalized, void* part, float* dist, int* idx, int64_t N, int D, int R,
+                          int k, int S, void* stream);
 /* Image scores at patch level (csrc/image_score.hip; PatchCore eq. 6-7 on cosine distances; the reference's patch-level branch
  * returns maps only).
  * ssad_rows_smallest_index adds a partial row sort: the bp = min(b, R) smallest (value, column) pairs of each row of m [Q][R],
@@ -543,11 +541,12 @@ int ssad_knn_reweight(const float* xs, const float* bank_normalized, const int* 
  * applied to the k winners only, so exact and near duplicates give finite distances >= 0.
  * ssad_row_sqnorms: out[n] = sum_j x[n][j]^2, one wave per row in one fixed order that does not depend on N or on where the row
  *   stands: equal rows give equal bits.  No atomics.
- * ssad_l2_knn_fused / _split / _index / _index_split: the four cosine entry points above with that distance -- out[n] = the mean of
- *   the k (1..3) smallest d, added smallest first; dist [N][k] / idx [N][k] = the k smallest (d2, bank row) pairs, lexicographic
- *   (equal d2 to the smaller row), dist = sqrtf(d2).  bank [R][D] not normalised, bank_sq [R] = ssad_row_sqnorms(bank).  part as in
- *   the cosine forms ([S][N][3] floats / 64-bit keys).  out, dist and idx are the same bits for every S and on every call, and the k
- *   distances of the index form average to out's bits.  D % 32 == 0, D <= 65536, k <= R, 1 <= S <= 65535.
+ * ssad_l2_knn_fused / _index: the cosine mean and index searches above with that distance -- out[n] = the mean of the k (1..3)
+ *   smallest d, added smallest first; dist [N][k] / idx [N][k] = the k smallest (d2, bank row) pairs, lexicographic (equal d2 to the
+ *   smaller row), dist = sqrtf(d2).  bank [R][D] not normalised, bank_sq [R] = ssad_row_sqnorms(bank).  S bank splits: 1 = one launch
+ *   (part unused, may be null); S > 1 = part [S][N][3] floats (fused) or 64-bit keys (index, 8-byte aligned), caller-owned, and a merge
+ *   launch.  out, dist and idx are the same bits for every S and on every call, and the k distances of the index form average to
+ *   out's bits.  D % 32 == 0, D <= 65536, k <= R, 1 <= S <= 65535.
  * ssad_l2_from_dots: out[q][r] = max(qsq[q] + bsq[r] - 2 sim[q][r], 0), SQUARED distances from dot products sim [Q][R] (the
  *   expression above; feeds ssad_rows_smallest_index with cosine = 0).  out may be sim.  Q <= 65535.
  * ssad_knn_reweight_l2: ssad_knn_reweight for this metric: d(x, r) = sqrt(sum_j (x[j] - bank[r][j])^2) by direct differences, the
@@ -555,13 +554,10 @@ int ssad_knn_reweight(const float* xs, const float* bank_normalized, const int* 
  *   bp neighbour distances (Euclidean distances are not bounded by 2; expf overflows above 88).  A row outside 0 .. R - 1 counts as
  *   distance 0.  1 <= bp <= 32. */
 int ssad_row_sqnorms(const float* x, float* out, int64_t N, int D, void* stream);
-int ssad_l2_knn_fused(const float* x, const float* bank, const float* bank_sq, float* out, int64_t N, int D, int R, int k, void* stream);
-int ssad_l2_knn_split(const float* x, const float* bank, const float* bank_sq, float* part, float* out, int64_t N, int D, int R, int k,
+int ssad_l2_knn_fused(const float* x, const float* bank, const float* bank_sq, float* part, float* out, int64_t N, int D, int R, int k,
                       int S, void* stream);
-int ssad_l2_knn_index(const float* x, const float* bank, const float* bank_sq, float* dist, int* idx, int64_t N, int D, int R, int k,
-                      void* stream);
-int ssad_l2_knn_index_split(const float* x, const float* bank, const float* bank_sq, void* part, float* dist, int* idx, int64_t N, int D,
-                            int R, int k, int S, void* stream);
+int ssad_l2_knn_index(const float* x, const float* bank, const float* bank_sq, void* part, float* dist, int* idx, int64_t N, int D,
+                      int R, int k, int S, void* stream);
 int ssad_l2_from_dots(const float* sim, const float* qsq, const float* bsq, float* out, int64_t Q, int R, void* stream);
 int ssad_knn_reweight_l2(const float* xs, const float* bank, const int* mstar, const int* nbr, const float* smax, float* out, int64_t Q,
                          int D, int R, int bp, void* stream);
@@ -571,18 +567,14 @@ int ssad_knn_reweight_l2(const float* xs, const float* bank, const int* mstar, c
  * flushed to signed zero: no half holds inf, NaN or a subnormal.
  * ssad_rows_to_half: xh[n][j] = h(x[n][j]) (xh: [N][D] halves) and sq[n] = sum_j xh[n][j]^2 in fp32 in ssad_row_sqnorms' order, one
  *   pass: equal rounded rows give equal norm bits wherever they stand.  D % 32 == 0, D <= 65536.
- * ssad_l2h_knn_fused / _split / _index / _index_split: the four ssad_l2_knn entry points on rounded rows -- xh [N][D] and bankh [R][D]
- *   halves (16-byte aligned), x_sq [N] and bank_sq [R] their norms from ssad_rows_to_half; out, dist, idx, part, S, k and the bit
- *   claims (the same bits for every S and on every call; the index form's distances average to out's bits) as there. */
+ * ssad_l2h_knn_fused / _index: ssad_l2_knn_fused / _index on rounded rows -- xh [N][D] and bankh [R][D] halves (16-byte aligned),
+ *   x_sq [N] and bank_sq [R] their norms from ssad_rows_to_half; out, dist, idx, part, S, k and the bit claims (the same bits for
+ *   every S and on every call; the index form's distances average to out's bits) as there. */
 int ssad_rows_to_half(const float* x, void* xh, float* sq, int64_t N, int D, void* stream);
-int ssad_l2h_knn_fused(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* out, int64_t N, int D, int R,
-                       int k, void* stream);
-int ssad_l2h_knn_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* part, float* out, int64_t N,
+int ssad_l2h_knn_fused(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* part, float* out, int64_t N,
                        int D, int R, int k, int S, void* stream);
-int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* dist, int* idx, int64_t N,
-                       int D, int R, int k, void* stream);
-int ssad_l2h_knn_index_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
-                             int* idx, int64_t N, int D, int R, int k, int S, void* stream);
+int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist, int* idx,
+                       int64_t N, int D, int R, int k, int S, void* stream);
 /* An 8-bit scalar-quantised bank for the flat Euclidean search (csrc/knn_l2_int8.hip; faiss' IndexScalarQuantizer, QT_8bit_uniform):
  * one affine code (lo, s) for the whole bank, c(x) = rint(min(max((x - lo) * inv_s, 0), 255)) - 128 in fp32 in that order (to nearest
  * even; NaN -> -128), stored as int8.  The distance is that BETWEEN THE CODES plus the query's clamp loss:

@@ -655,20 +655,11 @@ extern "C" int ssad_cosine_knn_split(const float* x, const float* bank_normalize
 
 // kneighbors of the cosine bank: for every query the k (1..3) smallest (distance, bank row) pairs in lexicographic order, ascending,
 // dist [N][k] float32 and idx [N][k] int32 -- the distances are the bits ssad_cosine_knn_fused averages, equal distances go to the
-// smaller row.  One launch; no atomics, the same bits on every call.  D a multiple of 32, at most 65536; R >= k.
-extern "C" int ssad_cosine_knn_index(const float* x, const float* bank_normalized, float* dist, int* idx, int64_t N, int D, int R, int k,
-                                     void* stream) {
-    SSAD_CHECK_ARG(x && bank_normalized && dist && idx && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_CHECK_ARG(D % BK == 0 && D <= 65536, "D must be a multiple of 32, at most 65536");
-    SSAD_CHECK_ARG(k >= 1 && k <= 3 && k <= R, "k in 1..3 and <= bank rows");
-    SSAD_CHECK_ARG(cdiv64(N, BQ) < (int64_t)2147483647, "too many rows for one launch");
-    return knn_index_launch(x, bank_normalized, nullptr, dist, idx, N, D, R, k, 1, stream);
-}
-
-// The bank-split form of ssad_cosine_knn_index (the split of ssad_cosine_knn_split): part [S][N][3] 64-bit keys (caller-owned, 8-byte
-// aligned), a second launch merges them.  dist and idx are the same bits for every S, S = 1 (which needs no part) included.
-extern "C" int ssad_cosine_knn_index_split(const float* x, const float* bank_normalized, void* part, float* dist, int* idx, int64_t N,
-                                           int D, int R, int k, int S, void* stream) {
+// smaller row.  S = 1: one launch, part unused (may be null).  S > 1: the bank split of ssad_cosine_knn_split, part [S][N][3] 64-bit keys
+// (caller-owned, 8-byte aligned), a second launch merges them.  No atomics; dist and idx are the same bits on every call and for every S.
+// D a multiple of 32, at most 65536; R >= k.
+extern "C" int ssad_cosine_knn_index(const float* x, const float* bank_normalized, void* part, float* dist, int* idx, int64_t N, int D,
+                                     int R, int k, int S, void* stream) {
     SSAD_CHECK_ARG(x && bank_normalized && dist && idx && N > 0 && D > 0 && R > 0, "bad argument");
     SSAD_CHECK_ARG(D % BK == 0 && D <= 65536, "D must be a multiple of 32, at most 65536");
     SSAD_CHECK_ARG(k >= 1 && k <= 3 && k <= R, "k in 1..3 and <= bank rows");

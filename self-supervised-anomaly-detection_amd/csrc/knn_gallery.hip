@@ -177,7 +177,7 @@ extern "C" int ssad_l2_direct(const float* q, const float* b, float* out, int64_
     return 0;
 }
 
-// ssad_l2_knn_fused / _split with the bank of query image q restricted to the blocks of gallery[q][0 .. K - 1]: out [Q P].
+// ssad_l2_knn_fused with the bank of query image q restricted to the blocks of gallery[q][0 .. K - 1]: out [Q P].
 extern "C" int ssad_l2_knn_gallery(const float* x, const float* bank, const float* bank_sq, const int* gallery, float* part, float* out,
                                    int Q, int P, int T, int K, int D, int k, int S, void* stream) {
     SSAD_CHECK_ARG(x && bank && bank_sq && gallery && out, "bad argument");
@@ -185,7 +185,7 @@ extern "C" int ssad_l2_knn_gallery(const float* x, const float* bank, const floa
     return l2_knn_gallery_launch<false>(GParams{x, bank, bank_sq, gallery, part, out, nullptr, nullptr, Q, P, T, K, D, k, 0}, S, stream);
 }
 
-// ssad_l2_knn_index / _index_split over the same galleries: dist / idx [Q P][k], idx the GLOBAL bank row; part: 64-bit keys.
+// ssad_l2_knn_index over the same galleries: dist / idx [Q P][k], idx the GLOBAL bank row; part: 64-bit keys.
 extern "C" int ssad_l2_knn_gallery_index(const float* x, const float* bank, const float* bank_sq, const int* gallery, void* part,
                                          float* dist, int* idx, int Q, int P, int T, int K, int D, int k, int S, void* stream) {
     SSAD_CHECK_ARG(x && bank && bank_sq && gallery && dist && idx, "bad argument");

@@ -3,8 +3,8 @@
 //   <q, b>       the MFMA chain of knn.hip's tile (same tile, same K order, same staging) on UNNORMALISED operands,
 //   |q|^2, |b|^2 one summation order (sqnorm_wave: lane-strided fma, xor butterfly) wherever they are taken, so equal rows give equal bits,
 //   d2           fmaxf((qn + bn) - 2 dot, 0) in the per-tile epilogue; the K loop is knn.hip's, untouched by the metric.
-// Selection runs on d2 (monotone in d); sqrtf is applied to the k winners only.  One kernel template serves the four entry points:
-// mean or (distance, row) keys, one launch (S = 1) or the bank split of ssad_cosine_knn_split with a merge launch.  The tile itself
+// Selection runs on d2 (monotone in d); sqrtf is applied to the k winners only.  One kernel template serves both entry points:
+// mean or (distance, row) keys, each one launch (S = 1) or the bank split of ssad_cosine_knn_split with a merge launch.  The tile itself
 // -- norms, K loop, epilogue, tail, result writers -- is knn_tile.h's; this file walks the bank with it.
 #include "knn_tile.h"
 
@@ -148,9 +148,12 @@ __global__ __launch_bounds__(NT) void knn_reweight_l2_kernel(const float* __rest
 
 }  // namespace
 
-#define SSAD_L2_KNN_CHECKS()                                                                                    \
+// KEYS: part holds 64-bit keys (the index form), else floats
+#define SSAD_L2_KNN_CHECKS(KEYS)                                                                                \
     SSAD_CHECK_ARG(D % BK == 0 && D <= 65536, "D must be a multiple of 32, at most 65536");                     \
     SSAD_CHECK_ARG(k >= 1 && k <= 3 && k <= R, "k in 1..3 and <= bank rows");                                   \
+    SSAD_CHECK_ARG(S >= 1 && S <= 65535 && (S == 1 || part), "S in 1..65535, with a workspace when S > 1");     \
+    SSAD_CHECK_ARG(!(KEYS) || ((uintptr_t)part & 7) == 0, "part must be 8-byte aligned");                       \
     SSAD_CHECK_ARG(cdiv64(N, BQ) < (int64_t)2147483647, "too many rows for one launch")
 
 // out[n] = sum x[n][:]^2 in fp32, one wave per row in one fixed order (independent of N and of the row's place): equal rows give equal bits.
@@ -163,40 +166,22 @@ extern "C" int ssad_row_sqnorms(const float* x, float* out, int64_t N, int D, vo
 }
 
 // out[n] = mean of the sqrt of the k (1..3) smallest d2 = max(|x_n|^2 + |b_r|^2 - 2 <x_n, b_r>, 0) over the R bank rows, added smallest
-// first; bank_sq = ssad_row_sqnorms(bank).  One launch.
-extern "C" int ssad_l2_knn_fused(const float* x, const float* bank, const float* bank_sq, float* out, int64_t N, int D, int R, int k,
-                                 void* stream) {
-    SSAD_CHECK_ARG(x && bank && bank_sq && out && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2_KNN_CHECKS();
-    return l2_knn_launch<false>(L2Params{x, bank, bank_sq, nullptr, out, nullptr, nullptr, N, D, R, 0, k}, 1, stream);
-}
-
-// The bank split of ssad_cosine_knn_split for ssad_l2_knn_fused: part [S][N][3] floats (caller-owned), a second launch merges them.
-// out is the same bits for every S.
-extern "C" int ssad_l2_knn_split(const float* x, const float* bank, const float* bank_sq, float* part, float* out, int64_t N, int D,
+// first; bank_sq = ssad_row_sqnorms(bank).  S = 1: one launch, part unused (may be null).  S > 1: the bank split of
+// ssad_cosine_knn_split, part [S][N][3] floats (caller-owned), a second launch merges them.  out is the same bits for every S.
+extern "C" int ssad_l2_knn_fused(const float* x, const float* bank, const float* bank_sq, float* part, float* out, int64_t N, int D,
                                  int R, int k, int S, void* stream) {
-    SSAD_CHECK_ARG(x && bank && bank_sq && part && out && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2_KNN_CHECKS();
-    SSAD_CHECK_ARG(S >= 1 && S <= 65535, "S in 1..65535");
+    SSAD_CHECK_ARG(x && bank && bank_sq && out && N > 0 && D > 0 && R > 0, "bad argument");
+    SSAD_L2_KNN_CHECKS(false);
     return l2_knn_launch<false>(L2Params{x, bank, bank_sq, part, out, nullptr, nullptr, N, D, R, 0, k}, S, stream);
 }
 
 // kneighbors of the Euclidean bank: the k smallest (d2, bank row) pairs of every query in lexicographic order, dist [N][k] = sqrt(d2)
-// and idx [N][k] int32 -- the distances are the bits ssad_l2_knn_fused averages, equal d2 go to the smaller row.  One launch.
-extern "C" int ssad_l2_knn_index(const float* x, const float* bank, const float* bank_sq, float* dist, int* idx, int64_t N, int D, int R,
-                                 int k, void* stream) {
+// and idx [N][k] int32 -- the distances are the bits ssad_l2_knn_fused averages, equal d2 go to the smaller row.  part [S][N][3]
+// 64-bit keys (caller-owned, 8-byte aligned) when S > 1; the same bits for every S.
+extern "C" int ssad_l2_knn_index(const float* x, const float* bank, const float* bank_sq, void* part, float* dist, int* idx, int64_t N,
+                                 int D, int R, int k, int S, void* stream) {
     SSAD_CHECK_ARG(x && bank && bank_sq && dist && idx && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2_KNN_CHECKS();
-    return l2_knn_launch<true>(L2Params{x, bank, bank_sq, nullptr, nullptr, dist, idx, N, D, R, 0, k}, 1, stream);
-}
-
-// The bank split of ssad_l2_knn_index: part [S][N][3] 64-bit keys (caller-owned, 8-byte aligned; not needed for S = 1).
-extern "C" int ssad_l2_knn_index_split(const float* x, const float* bank, const float* bank_sq, void* part, float* dist, int* idx,
-                                       int64_t N, int D, int R, int k, int S, void* stream) {
-    SSAD_CHECK_ARG(x && bank && bank_sq && dist && idx && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2_KNN_CHECKS();
-    SSAD_CHECK_ARG(S >= 1 && S <= 65535 && (S == 1 || part), "S in 1..65535, with a workspace when S > 1");
-    SSAD_CHECK_ARG(((uintptr_t)part & 7) == 0, "part must be 8-byte aligned");
+    SSAD_L2_KNN_CHECKS(true);
     return l2_knn_launch<true>(L2Params{x, bank, bank_sq, part, nullptr, dist, idx, N, D, R, 0, k}, S, stream);
 }
 

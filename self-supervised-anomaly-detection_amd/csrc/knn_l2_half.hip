@@ -183,10 +183,13 @@ static int l2h_knn_launch(L2hParams p, int S, void* stream) {
 
 }  // namespace
 
-#define SSAD_L2H_KNN_CHECKS()                                                                                   \
+// KEYS: part holds 64-bit keys (the index form), else floats
+#define SSAD_L2H_KNN_CHECKS(KEYS)                                                                               \
     SSAD_CHECK_ARG(D % 32 == 0 && D <= 65536, "D must be a multiple of 32, at most 65536");                     \
     SSAD_CHECK_ARG(k >= 1 && k <= 3 && k <= R, "k in 1..3 and <= bank rows");                                   \
     SSAD_CHECK_ARG((((uintptr_t)xh | (uintptr_t)bankh) & 15) == 0, "half rows must be 16-byte aligned");        \
+    SSAD_CHECK_ARG(S >= 1 && S <= 65535 && (S == 1 || part), "S in 1..65535, with a workspace when S > 1");     \
+    SSAD_CHECK_ARG(!(KEYS) || ((uintptr_t)part & 7) == 0, "part must be 8-byte aligned");                       \
     SSAD_CHECK_ARG(cdiv64(N, BQ) < (int64_t)2147483647, "too many rows for one launch")
 
 // xh[n][j] = h(x[n][j]) (fp32 -> fp16, round to nearest even, saturating at +-65504, subnormal results flushed to signed zero) and
@@ -200,41 +203,22 @@ extern "C" int ssad_rows_to_half(const float* x, void* xh, float* sq, int64_t N,
     return 0;
 }
 
-// ssad_l2_knn_fused on rounded rows: xh / bankh halves, x_sq / bank_sq their squared norms (ssad_rows_to_half).  One launch.
-extern "C" int ssad_l2h_knn_fused(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* out, int64_t N,
-                                  int D, int R, int k, void* stream) {
-    SSAD_CHECK_ARG(xh && x_sq && bankh && bank_sq && out && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2H_KNN_CHECKS();
-    return l2h_knn_launch<false>(L2hParams{(const hf*)xh, x_sq, (const hf*)bankh, bank_sq, nullptr, out, nullptr, nullptr, N, D, R, 0, k},
-                                 1, stream);
-}
-
-// The bank split of ssad_l2_knn_split: part [S][N][3] floats (caller-owned), a second launch merges them; the same bits for every S.
-extern "C" int ssad_l2h_knn_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* part, float* out,
+// ssad_l2_knn_fused on rounded rows: xh / bankh halves, x_sq / bank_sq their squared norms (ssad_rows_to_half).  part [S][N][3] floats
+// (caller-owned) when S > 1, merged by a second launch; the same bits for every S.
+extern "C" int ssad_l2h_knn_fused(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* part, float* out,
                                   int64_t N, int D, int R, int k, int S, void* stream) {
-    SSAD_CHECK_ARG(xh && x_sq && bankh && bank_sq && part && out && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2H_KNN_CHECKS();
-    SSAD_CHECK_ARG(S >= 1 && S <= 65535, "S in 1..65535");
+    SSAD_CHECK_ARG(xh && x_sq && bankh && bank_sq && out && N > 0 && D > 0 && R > 0, "bad argument");
+    SSAD_L2H_KNN_CHECKS(false);
     return l2h_knn_launch<false>(L2hParams{(const hf*)xh, x_sq, (const hf*)bankh, bank_sq, part, out, nullptr, nullptr, N, D, R, 0, k}, S,
                                  stream);
 }
 
-// kneighbors on rounded rows: the k smallest (d2, bank row) pairs, dist = sqrt(d2) -- the bits ssad_l2h_knn_fused averages.
-extern "C" int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, float* dist, int* idx,
-                                  int64_t N, int D, int R, int k, void* stream) {
+// kneighbors on rounded rows: the k smallest (d2, bank row) pairs, dist = sqrt(d2) -- the bits ssad_l2h_knn_fused averages.  part
+// [S][N][3] 64-bit keys (caller-owned, 8-byte aligned) when S > 1; the same bits for every S.
+extern "C" int ssad_l2h_knn_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
+                                  int* idx, int64_t N, int D, int R, int k, int S, void* stream) {
     SSAD_CHECK_ARG(xh && x_sq && bankh && bank_sq && dist && idx && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2H_KNN_CHECKS();
-    return l2h_knn_launch<true>(L2hParams{(const hf*)xh, x_sq, (const hf*)bankh, bank_sq, nullptr, nullptr, dist, idx, N, D, R, 0, k}, 1,
-                                stream);
-}
-
-// The bank split of ssad_l2h_knn_index: part [S][N][3] 64-bit keys (caller-owned, 8-byte aligned; not needed for S = 1).
-extern "C" int ssad_l2h_knn_index_split(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part,
-                                        float* dist, int* idx, int64_t N, int D, int R, int k, int S, void* stream) {
-    SSAD_CHECK_ARG(xh && x_sq && bankh && bank_sq && dist && idx && N > 0 && D > 0 && R > 0, "bad argument");
-    SSAD_L2H_KNN_CHECKS();
-    SSAD_CHECK_ARG(S >= 1 && S <= 65535 && (S == 1 || part), "S in 1..65535, with a workspace when S > 1");
-    SSAD_CHECK_ARG(((uintptr_t)part & 7) == 0, "part must be 8-byte aligned");
+    SSAD_L2H_KNN_CHECKS(true);
     return l2h_knn_launch<true>(L2hParams{(const hf*)xh, x_sq, (const hf*)bankh, bank_sq, part, nullptr, dist, idx, N, D, R, 0, k}, S,
                                 stream);
 }

@@ -47,24 +47,19 @@ SIGNATURES = {
     "ssad_cosine_knn_mean": [_c_fp, _c_fp, _c_l, _c_i, _c_i, _c_fp],
     "ssad_cosine_knn_fused": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     "ssad_cosine_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_cosine_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_cosine_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_cosine_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_rows_smallest_index": [_c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_fp],
     "ssad_rows_argmax": [_c_fp, _c_l, _c_i, _c_fp, _c_fp, _c_fp],
     "ssad_knn_reweight": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     "ssad_row_sqnorms": [_c_fp, _c_fp, _c_l, _c_i, _c_fp],
-    "ssad_l2_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_l2_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_l2_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_l2_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     "ssad_l2_from_dots": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_fp],
     "ssad_knn_reweight_l2": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
     # half-precision operands for the flat Euclidean search (csrc/knn_l2_half.hip)
     "ssad_rows_to_half": [_c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_fp],
-    "ssad_l2h_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_l2h_knn_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_l2h_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp],
-    "ssad_l2h_knn_index_split": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2h_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
+    "ssad_l2h_knn_index": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_fp],
     # an 8-bit scalar-quantised bank for the flat Euclidean search (csrc/knn_l2_int8.hip)
     "ssad_rows_to_int8": [_c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_f, _c_f, _c_f, _c_fp],
     "ssad_l2q_knn_fused": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_fp],

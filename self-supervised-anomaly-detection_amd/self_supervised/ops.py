@@ -759,8 +759,8 @@ def cosine_knn_fused(x, bank_n, k=3):
 def cosine_knn_index(x, bank_n, k=3, splits=None):
     """kneighbors of the cosine bank: x [N][D] (not normalised), bank_n [R][D] L2-normalised -> (dist [N][k] float32, idx [N][k]
     int32), the k (1..3) smallest (distance, bank row) pairs of every query, ascending, equal distances to the smaller row
-    (csrc/knn.hip ssad_cosine_knn_index / _split).  The distances are the bits cosine_knn_fused averages.  `splits`: None = the
-    knn_splits rule of cosine_knn_fused; S >= 1 = that many bank splits (1: the one-launch kernel); same bits for every S."""
+    (csrc/knn.hip ssad_cosine_knn_index).  The distances are the bits cosine_knn_fused averages.  `splits`: None = the knn_splits
+    rule of cosine_knn_fused; S >= 1 = that many bank splits (1: one launch); same bits for every S."""
     n, d = x.shape
     r = bank_n.shape[0]
     k = int(k)
@@ -773,16 +773,10 @@ def cosine_knn_index(x, bank_n, k=3, splits=None):
         raise ValueError(f"cosine_knn_index: splits must be >= 1, got {s}")
     dist = _new((n, k), x)
     idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
-    i32 = torch.int32
-    if s == 1:
-        _run("knn_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + 2 * n * k),
-             lambda: _hip.lib().ssad_cosine_knn_index(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d, r, k,
-                                                      _hip.stream()))
-        return dist, idx
-    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64)       # (distance bits << 32 | row) keys
-    _run("knn_index_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + 2 * n * k) + 16.0 * part.numel(),
-         lambda: _hip.lib().ssad_cosine_knn_index_split(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(part, dtype=torch.int64), _hip.ptr(dist),
-                                                        _hip.ptr(idx, dtype=i32), n, d, r, k, s, _hip.stream()))
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64) if s > 1 else None     # (distance bits << 32 | row) keys
+    _run("knn_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank_n.numel() + 2 * n * k) + 16.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_cosine_knn_index(_hip.ptr(x), _hip.ptr(bank_n), _hip.ptr(part, True, torch.int64), _hip.ptr(dist),
+                                                  _hip.ptr(idx, dtype=torch.int32), n, d, r, k, s, _hip.stream()))
     return dist, idx
 
 
@@ -890,39 +884,28 @@ def _l2_flat_args(name, x, bank, bank_sq, k, splits, bank_dtype, k_range=(1, 3))
 
 def l2_knn_fused(x, bank, bank_sq, k=3, splits=None):
     """x [N][D], bank [R][D] (neither normalised), bank_sq = row_sqnorms(bank) -> [N] mean of the k smallest Euclidean distances
-    sqrt(max(|x|^2 + |b|^2 - 2 <x, b>, 0)) (csrc/knn_l2.hip ssad_l2_knn_fused / _split).  `splits`: None = the knn_splits rule; S >= 1 =
-    that many bank splits (1: one launch); the same bits for every S."""
+    sqrt(max(|x|^2 + |b|^2 - 2 <x, b>, 0)) (csrc/knn_l2.hip ssad_l2_knn_fused).  `splits`: None = the knn_splits rule; S >= 1 = that
+    many bank splits (1: one launch); the same bits for every S."""
     n, d, r, k, s = _l2_flat_args("l2_knn_fused", x, bank, bank_sq, k, splits, torch.float32)
     out = _new((n,), x)
-    if s == 1:
-        _run("l2_knn_fused", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n),
-             lambda: _hip.lib().ssad_l2_knn_fused(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(out), n, d, r, k,
-                                                  _hip.stream()))
-        return out
-    part = _new((s, n, 3), x)
-    _run("l2_knn_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n + 6 * part.numel()),
-         lambda: _hip.lib().ssad_l2_knn_split(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part), _hip.ptr(out), n, d, r, k,
-                                              s, _hip.stream()))
+    part = _new((s, n, 3), x) if s > 1 else None
+    _run("l2_knn_fused", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + n) + 24.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_l2_knn_fused(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part, True), _hip.ptr(out), n, d, r,
+                                              k, s, _hip.stream()))
     return out
 
 
 def l2_knn_index(x, bank, bank_sq, k=3, splits=None):
     """kneighbors of the Euclidean bank: (dist [N][k] float32, idx [N][k] int32), the k (1..3) smallest (squared distance, bank row)
     pairs of every query, ascending, equal ones to the smaller row; dist holds the roots -- the bits l2_knn_fused averages
-    (csrc/knn_l2.hip ssad_l2_knn_index / _split).  `splits` as in l2_knn_fused."""
+    (csrc/knn_l2.hip ssad_l2_knn_index).  `splits` as in l2_knn_fused."""
     n, d, r, k, s = _l2_flat_args("l2_knn_index", x, bank, bank_sq, k, splits, torch.float32)
     dist = _new((n, k), x)
     idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
-    i32 = torch.int32
-    if s == 1:
-        _run("l2_knn_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + 2 * n * k),
-             lambda: _hip.lib().ssad_l2_knn_index(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(dist), _hip.ptr(idx, dtype=i32),
-                                                  n, d, r, k, _hip.stream()))
-        return dist, idx
-    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64)       # (squared-distance bits << 32 | row) keys
-    _run("l2_knn_index_split", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + 2 * n * k) + 16.0 * part.numel(),
-         lambda: _hip.lib().ssad_l2_knn_index_split(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part, dtype=torch.int64),
-                                                    _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d, r, k, s, _hip.stream()))
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64) if s > 1 else None     # (squared-distance bits << 32 | row) keys
+    _run("l2_knn_index", 2.0 * n * d * r, 4.0 * (x.numel() + bank.numel() + r + 2 * n * k) + 16.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_l2_knn_index(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(bank_sq), _hip.ptr(part, True, torch.int64),
+                                              _hip.ptr(dist), _hip.ptr(idx, dtype=torch.int32), n, d, r, k, s, _hip.stream()))
     return dist, idx
 
 
@@ -942,19 +925,13 @@ def rows_to_half(x):
 def l2h_knn_fused(x, bank_h, bank_sq, k=3, splits=None):
     """l2_knn_fused with half-precision operands: x [N][D] fp32 queries (rounded here, rows_to_half), (bank_h, bank_sq) =
     rows_to_half(bank) -> [N] mean of the k smallest distances BETWEEN THE ROUNDED ROWS, sqrt(max(|h(x)|^2 + |h(b)|^2 - 2 <h(x), h(b)>,
-    0)), on the fp16 matrix cores (csrc/knn_l2_half.hip ssad_l2h_knn_fused / _split).  `splits` as in l2_knn_fused; the same bits for
-    every S."""
+    0)), on the fp16 matrix cores (csrc/knn_l2_half.hip ssad_l2h_knn_fused).  `splits` as in l2_knn_fused; the same bits for every S."""
     n, d, r, k, s = _l2_flat_args("l2h_knn_fused", x, bank_h, bank_sq, k, splits, torch.float16)
     xh, xsq = rows_to_half(x)
     out = _new((n,), x)
-    if s == 1:
-        _run("l2h_knn_fused", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + 2 * n),
-             lambda: _hip.lib().ssad_l2h_knn_fused(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(out), n, d,
-                                                   r, k, _hip.stream()))
-        return out
-    part = _new((s, n, 3), x)
-    _run("l2h_knn_split", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + 2 * n + 6 * part.numel()),
-         lambda: _hip.lib().ssad_l2h_knn_split(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(part),
+    part = _new((s, n, 3), x) if s > 1 else None
+    _run("l2h_knn_fused", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + 2 * n) + 24.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_l2h_knn_fused(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(part, True),
                                                _hip.ptr(out), n, d, r, k, s, _hip.stream()))
     return out
 
@@ -962,22 +939,16 @@ def l2h_knn_fused(x, bank_h, bank_sq, k=3, splits=None):
 def l2h_knn_index(x, bank_h, bank_sq, k=3, splits=None):
     """l2_knn_index with half-precision operands (arguments as l2h_knn_fused): (dist [N][k] float32, idx [N][k] int32), the k smallest
     (squared distance, bank row) pairs between the rounded rows, equal ones to the smaller row; dist holds the bits l2h_knn_fused
-    averages (csrc/knn_l2_half.hip ssad_l2h_knn_index / _split)."""
+    averages (csrc/knn_l2_half.hip ssad_l2h_knn_index)."""
     n, d, r, k, s = _l2_flat_args("l2h_knn_index", x, bank_h, bank_sq, k, splits, torch.float16)
     xh, xsq = rows_to_half(x)
     dist = _new((n, k), x)
     idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
-    i32 = torch.int32
-    if s == 1:
-        _run("l2h_knn_index", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + n + 2 * n * k),
-             lambda: _hip.lib().ssad_l2h_knn_index(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq), _hip.ptr(dist),
-                                                   _hip.ptr(idx, dtype=i32), n, d, r, k, _hip.stream()))
-        return dist, idx
-    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64)       # (squared-distance bits << 32 | row) keys
-    _run("l2h_knn_index_split", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + n + 2 * n * k) + 16.0 * part.numel(),
-         lambda: _hip.lib().ssad_l2h_knn_index_split(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq),
-                                                     _hip.ptr(part, dtype=torch.int64), _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d,
-                                                     r, k, s, _hip.stream()))
+    part = torch.empty((s, n, 3), device=x.device, dtype=torch.int64) if s > 1 else None     # (squared-distance bits << 32 | row) keys
+    _run("l2h_knn_index", 2.0 * n * d * r, 2.0 * (x.numel() + bank_h.numel()) + 4.0 * (r + n + 2 * n * k) + 16.0 * (s > 1) * s * n * 3,
+         lambda: _hip.lib().ssad_l2h_knn_index(_hip.hptr(xh), _hip.ptr(xsq), _hip.hptr(bank_h), _hip.ptr(bank_sq),
+                                               _hip.ptr(part, True, torch.int64), _hip.ptr(dist), _hip.ptr(idx, dtype=torch.int32), n, d, r,
+                                               k, s, _hip.stream()))
     return dist, idx
 
 

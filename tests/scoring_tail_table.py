@@ -648,10 +648,7 @@ def run_zero_norm(dev):
             ar = Arena(dev)
             o = {"dist": ar.out("dist", (n, k), torch.float32), "idx": ar.out("idx", (n, k), torch.int32)}
             part = ar.out("part", (2, n, 3), torch.int64, all_written=False)
-            if s == 1:
-                hip.check(lib.ssad_cosine_knn_index(_p(xd), _p(bnd), _p(o["dist"]), _p(o["idx"]), n, d, r, k, st))
-            else:
-                hip.check(lib.ssad_cosine_knn_index_split(_p(xd), _p(bnd), _p(part), _p(o["dist"]), _p(o["idx"]), n, d, r, k, s, st))
+            hip.check(lib.ssad_cosine_knn_index(_p(xd), _p(bnd), _p(part), _p(o["dist"]), _p(o["idx"]), n, d, r, k, s, st))
             ar.check_outputs(name)
             return o
         o = twice(name, launch)

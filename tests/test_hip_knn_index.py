@@ -1,4 +1,4 @@
-"""GPU tests of the index-returning cosine kNN (csrc/knn.hip ssad_cosine_knn_index / _split), the row selection, the image scores
+"""GPU tests of the index-returning cosine kNN (csrc/knn.hip ssad_cosine_knn_index), the row selection, the image scores
 built on them (csrc/image_score.hip) and their way through AnomalyDetector, tools.inference and tools.sweep.  The reference
 everywhere is the float64 numpy brute force of tests/knn_index_ref.py on the same fp32 inputs; two HIP paths are compared with
 each other only where bit-equality between them is the claim."""
@@ -170,7 +170,7 @@ def test_argument_errors_of_the_index_kernel():
         ops.cosine_knn_index(x, bank, 3)
     idx = torch.empty((5, 3), device="cuda", dtype=torch.int32)
     dist = torch.empty((5, 3), device="cuda")
-    rc = _hip.lib().ssad_cosine_knn_index(x.data_ptr(), bank.data_ptr(), dist.data_ptr(), idx.data_ptr(), 5, 64, 2, 3, _hip.stream())
+    rc = _hip.lib().ssad_cosine_knn_index(x.data_ptr(), bank.data_ptr(), None, dist.data_ptr(), idx.data_ptr(), 5, 64, 2, 3, 1, _hip.stream())
     assert rc == 2 and b"k in 1..3" in _hip.lib().ssad_last_error()
 
 

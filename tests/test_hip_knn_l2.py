@@ -1,5 +1,5 @@
-"""GPU tests of the Euclidean metric of the kNN detector: csrc/knn_l2.hip (ssad_row_sqnorms, ssad_l2_knn_fused / _split / _index /
-_index_split, ssad_l2_from_dots, ssad_knn_reweight_l2) and its way through AnomalyDetector(metric='euclidean'), tools.inference and
+"""GPU tests of the Euclidean metric of the kNN detector: csrc/knn_l2.hip (ssad_row_sqnorms, ssad_l2_knn_fused / _index,
+ssad_l2_from_dots, ssad_knn_reweight_l2) and its way through AnomalyDetector(metric='euclidean'), tools.inference and
 tools.sweep.  The reference everywhere is the float64 numpy brute force of tests/knn_l2_ref.py on the same fp32 inputs; two HIP
 paths are compared with each other only where bit-equality between them is the claim.
 
@@ -60,32 +60,26 @@ def guards_intact(buf):
 
 
 def raw_knn(x, bank, bsq, k, splits=None, index=False):
-    """The C entry points on caller-owned, guarded outputs.  splits None: the one-launch entries; S: the split entries.  Returns the
-    output views (out,) or (dist, idx) after checking the guard rows."""
+    """The C entry points on caller-owned, guarded outputs.  splits None: one launch without a workspace; S: S splits with one.  Returns
+    the output views (out,) or (dist, idx) after checking the guard rows."""
     from self_supervised import _hip
     L = _hip.lib()
     n, d = x.shape
     r = bank.shape[0]
     st = _hip.stream()
+    s = splits or 1
+    ws = None if splits is None else torch.empty((s, n, 3), dtype=torch.int64 if index else torch.float32, device="cuda")
+    part = None if ws is None else ws.data_ptr()
     if index:
         dbuf, dist = guarded_out((n, k))
         ibuf, idx = guarded_out((n, k), torch.int32)
-        if splits is None:
-            rc = L.ssad_l2_knn_index(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), dist.data_ptr(), idx.data_ptr(), n, d, r, k, st)
-        else:
-            part = torch.empty((splits, n, 3), dtype=torch.int64, device="cuda")
-            rc = L.ssad_l2_knn_index_split(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), part.data_ptr(), dist.data_ptr(), idx.data_ptr(),
-                                           n, d, r, k, splits, st)
+        rc = L.ssad_l2_knn_index(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), part, dist.data_ptr(), idx.data_ptr(), n, d, r, k, s, st)
         assert rc == 0, L.ssad_last_error()
         torch.cuda.synchronize()
         assert guards_intact(dbuf) and guards_intact(ibuf)
         return dist, idx
     obuf, out = guarded_out((n,))
-    if splits is None:
-        rc = L.ssad_l2_knn_fused(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), out.data_ptr(), n, d, r, k, st)
-    else:
-        part = torch.empty((splits, n, 3), dtype=torch.float32, device="cuda")
-        rc = L.ssad_l2_knn_split(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), part.data_ptr(), out.data_ptr(), n, d, r, k, splits, st)
+    rc = L.ssad_l2_knn_fused(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), part, out.data_ptr(), n, d, r, k, s, st)
     assert rc == 0, L.ssad_last_error()
     torch.cuda.synchronize()
     assert guards_intact(obuf)
@@ -341,20 +335,32 @@ def test_argument_errors_leave_the_outputs_untouched():
         (P(x), P(bank), P(bsq), 48, 4, 3), (P(x), P(bank), P(bsq), 65536 + 32, 4, 3), (P(x), P(bank), P(bsq), 64, 4, 0),
         (P(x), P(bank), P(bsq), 64, 4, 4), (P(x), P(bank), P(bsq), 64, 2, 3)]
     for xa, ba, sa, d, r, k in bad:
-        assert L.ssad_l2_knn_fused(xa, ba, sa, P(out), 5, d, r, k, st) == 2
-        assert L.ssad_l2_knn_split(xa, ba, sa, P(partf), P(out), 5, d, r, k, 2, st) == 2
-        assert L.ssad_l2_knn_index(xa, ba, sa, P(dist), P(idx), 5, d, r, k, st) == 2
-        assert L.ssad_l2_knn_index_split(xa, ba, sa, P(partk), P(dist), P(idx), 5, d, r, k, 2, st) == 2
-    assert L.ssad_l2_knn_fused(P(x), P(bank), P(bsq), None, 5, 64, 4, 3, st) == 2
-    assert L.ssad_l2_knn_index(P(x), P(bank), P(bsq), P(dist), None, 5, 64, 4, 3, st) == 2
-    assert L.ssad_l2_knn_split(P(x), P(bank), P(bsq), None, P(out), 5, 64, 4, 3, 2, st) == 2
-    assert L.ssad_l2_knn_index_split(P(x), P(bank), P(bsq), None, P(dist), P(idx), 5, 64, 4, 3, 2, st) == 2
-    assert L.ssad_l2_knn_split(P(x), P(bank), P(bsq), P(partf), P(out), 5, 64, 4, 3, 0, st) == 2
+        assert L.ssad_l2_knn_fused(xa, ba, sa, None, P(out), 5, d, r, k, 1, st) == 2
+        assert L.ssad_l2_knn_fused(xa, ba, sa, P(partf), P(out), 5, d, r, k, 2, st) == 2
+        assert L.ssad_l2_knn_index(xa, ba, sa, None, P(dist), P(idx), 5, d, r, k, 1, st) == 2
+        assert L.ssad_l2_knn_index(xa, ba, sa, P(partk), P(dist), P(idx), 5, d, r, k, 2, st) == 2
+    good = (P(x), P(bank), P(bsq))
+    assert L.ssad_l2_knn_fused(*good, None, None, 5, 64, 4, 3, 1, st) == 2
+    assert L.ssad_l2_knn_index(*good, None, P(dist), None, 5, 64, 4, 3, 1, st) == 2
+    assert L.ssad_l2_knn_fused(*good, None, P(out), 5, 64, 4, 3, 2, st) == 2
+    assert L.ssad_l2_knn_index(*good, None, P(dist), P(idx), 5, 64, 4, 3, 2, st) == 2
+    assert L.ssad_l2_knn_fused(*good, P(partf), P(out), 5, 64, 4, 3, 0, st) == 2
+    assert L.ssad_l2_knn_index(*good, P(partk), P(dist), P(idx), 5, 64, 4, 3, 0, st) == 2
+    assert L.ssad_l2_knn_index(*good, P(partk) + 4, P(dist), P(idx), 5, 64, 4, 3, 2, st) == 2 and b"8-byte" in L.ssad_last_error()
     assert L.ssad_row_sqnorms(None, P(out), 5, 64, st) == 2 and L.ssad_row_sqnorms(P(x), None, 5, 64, st) == 2
-    assert L.ssad_l2_knn_index(P(x), P(bank), P(bsq), P(dist), P(idx), 5, 64, 2, 3, st) == 2 and b"k in 1..3" in L.ssad_last_error()
+    assert L.ssad_l2_knn_index(*good, None, P(dist), P(idx), 5, 64, 2, 3, 1, st) == 2 and b"k in 1..3" in L.ssad_last_error()
     torch.cuda.synchronize()
     assert torch.isnan(out).all() and torch.isnan(dist).all() and (idx == -7).all()
     assert torch.isnan(partf).all() and (partk == -7).all()
+    # S = 1 needs no workspace: a null part is accepted and gives the bits of the run with one
+    out2, dist2, idx2 = out.clone(), dist.clone(), idx.clone()
+    assert L.ssad_l2_knn_fused(*good, None, P(out), 5, 64, 4, 3, 1, st) == 0
+    assert L.ssad_l2_knn_fused(*good, P(partf), P(out2), 5, 64, 4, 3, 1, st) == 0
+    assert L.ssad_l2_knn_index(*good, None, P(dist), P(idx), 5, 64, 4, 3, 1, st) == 0
+    assert L.ssad_l2_knn_index(*good, P(partk), P(dist2), P(idx2), 5, 64, 4, 3, 1, st) == 0
+    torch.cuda.synchronize()
+    assert not torch.isnan(out).any() and (idx >= 0).all()
+    assert torch.equal(out, out2) and torch.equal(dist, dist2) and torch.equal(idx, idx2)
     with pytest.raises(ValueError, match="fewer than k"):
         ops.l2_knn_index(x, bank[:2], bsq[:2], 3)
     with pytest.raises(ValueError, match="multiple of 32"):

@@ -1,5 +1,5 @@
 """GPU tests of the flat Euclidean search with half-precision operands: csrc/knn_l2_half.hip (ssad_rows_to_half, ssad_l2h_knn_fused /
-_split / _index / _index_split) and its way through AnomalyDetector(bank_dtype='float16') and tools.inference.  The reference
+_index) and its way through AnomalyDetector(bank_dtype='float16') and tools.inference.  The reference
 everywhere is the float64 numpy brute force of tests/knn_l2_half_ref.py ON THE ROUNDED ROWS (the reference applies the same h); two HIP
 paths are compared with each other only where bit-equality between them is the claim.
 
@@ -82,31 +82,26 @@ def raw_to_half(rows):
 
 
 def raw_knn(xh, xsq, bh, bsq, k, splits=None, index=False):
-    """The C entry points on caller-owned, guarded outputs.  splits None: the one-launch entries; S: the split entries."""
+    """The C entry points on caller-owned, guarded outputs.  splits None: one launch without a workspace; S: S splits with one."""
     from self_supervised import _hip
     L = _hip.lib()
     n, d = xh.shape
     r = bh.shape[0]
     st = _hip.stream()
     P = lambda t: t.data_ptr()
+    s = splits or 1
+    ws = None if splits is None else torch.empty((s, n, 3), dtype=torch.int64 if index else torch.float32, device="cuda")
+    part = None if ws is None else P(ws)
     if index:
         dbuf, dist = guarded_out((n, k))
         ibuf, idx = guarded_out((n, k), torch.int32)
-        if splits is None:
-            rc = L.ssad_l2h_knn_index(P(xh), P(xsq), P(bh), P(bsq), P(dist), P(idx), n, d, r, k, st)
-        else:
-            part = torch.empty((splits, n, 3), dtype=torch.int64, device="cuda")
-            rc = L.ssad_l2h_knn_index_split(P(xh), P(xsq), P(bh), P(bsq), P(part), P(dist), P(idx), n, d, r, k, splits, st)
+        rc = L.ssad_l2h_knn_index(P(xh), P(xsq), P(bh), P(bsq), part, P(dist), P(idx), n, d, r, k, s, st)
         assert rc == 0, L.ssad_last_error()
         torch.cuda.synchronize()
         assert guards_intact(dbuf) and guards_intact(ibuf)
         return dist, idx
     obuf, out = guarded_out((n,))
-    if splits is None:
-        rc = L.ssad_l2h_knn_fused(P(xh), P(xsq), P(bh), P(bsq), P(out), n, d, r, k, st)
-    else:
-        part = torch.empty((splits, n, 3), dtype=torch.float32, device="cuda")
-        rc = L.ssad_l2h_knn_split(P(xh), P(xsq), P(bh), P(bsq), P(part), P(out), n, d, r, k, splits, st)
+    rc = L.ssad_l2h_knn_fused(P(xh), P(xsq), P(bh), P(bsq), part, P(out), n, d, r, k, s, st)
     assert rc == 0, L.ssad_last_error()
     torch.cuda.synchronize()
     assert guards_intact(obuf)
@@ -409,17 +404,18 @@ def test_argument_errors_leave_the_outputs_untouched():
            good[:3] + (None, 64, 4, 3), good + (48, 4, 3), good + (65536 + 32, 4, 3), good + (64, 4, 0), good + (64, 4, 4),
            good + (64, 2, 3)]
     for xa, qa, ba, sa, d, r, k in bad:
-        assert L.ssad_l2h_knn_fused(xa, qa, ba, sa, P(out), 5, d, r, k, st) == 2
-        assert L.ssad_l2h_knn_split(xa, qa, ba, sa, P(partf), P(out), 5, d, r, k, 2, st) == 2
-        assert L.ssad_l2h_knn_index(xa, qa, ba, sa, P(dist), P(idx), 5, d, r, k, st) == 2
-        assert L.ssad_l2h_knn_index_split(xa, qa, ba, sa, P(partk), P(dist), P(idx), 5, d, r, k, 2, st) == 2
-    assert L.ssad_l2h_knn_fused(*good, None, 5, 64, 4, 3, st) == 2
-    assert L.ssad_l2h_knn_index(*good, P(dist), None, 5, 64, 4, 3, st) == 2
-    assert L.ssad_l2h_knn_split(*good, None, P(out), 5, 64, 4, 3, 2, st) == 2
-    assert L.ssad_l2h_knn_index_split(*good, None, P(dist), P(idx), 5, 64, 4, 3, 2, st) == 2
-    assert L.ssad_l2h_knn_split(*good, P(partf), P(out), 5, 64, 4, 3, 0, st) == 2
-    assert L.ssad_l2h_knn_index_split(*good, P(partk), P(dist), P(idx), 5, 64, 4, 3, 0, st) == 2
-    assert L.ssad_l2h_knn_index(*good, P(dist), P(idx), 5, 64, 2, 3, st) == 2 and b"k in 1..3" in L.ssad_last_error()
+        assert L.ssad_l2h_knn_fused(xa, qa, ba, sa, None, P(out), 5, d, r, k, 1, st) == 2
+        assert L.ssad_l2h_knn_fused(xa, qa, ba, sa, P(partf), P(out), 5, d, r, k, 2, st) == 2
+        assert L.ssad_l2h_knn_index(xa, qa, ba, sa, None, P(dist), P(idx), 5, d, r, k, 1, st) == 2
+        assert L.ssad_l2h_knn_index(xa, qa, ba, sa, P(partk), P(dist), P(idx), 5, d, r, k, 2, st) == 2
+    assert L.ssad_l2h_knn_fused(*good, None, None, 5, 64, 4, 3, 1, st) == 2
+    assert L.ssad_l2h_knn_index(*good, None, P(dist), None, 5, 64, 4, 3, 1, st) == 2
+    assert L.ssad_l2h_knn_fused(*good, None, P(out), 5, 64, 4, 3, 2, st) == 2
+    assert L.ssad_l2h_knn_index(*good, None, P(dist), P(idx), 5, 64, 4, 3, 2, st) == 2
+    assert L.ssad_l2h_knn_fused(*good, P(partf), P(out), 5, 64, 4, 3, 0, st) == 2
+    assert L.ssad_l2h_knn_index(*good, P(partk), P(dist), P(idx), 5, 64, 4, 3, 0, st) == 2
+    assert L.ssad_l2h_knn_index(*good, P(partk) + 4, P(dist), P(idx), 5, 64, 4, 3, 2, st) == 2 and b"8-byte" in L.ssad_last_error()
+    assert L.ssad_l2h_knn_index(*good, None, P(dist), P(idx), 5, 64, 2, 3, 1, st) == 2 and b"k in 1..3" in L.ssad_last_error()
     src = gauss(5, 64, 1).cuda()
     for args in [(None, P(half_out), P(out), 5, 64), (P(src), None, P(out), 5, 64), (P(src), P(half_out), None, 5, 64),
                  (P(src), P(half_out), P(out), 5, 48), (P(src), P(half_out), P(out), 0, 64), (P(src), P(half_out), P(out), 5, 65536 + 32)]:
@@ -429,6 +425,15 @@ def test_argument_errors_leave_the_outputs_untouched():
     assert torch.isnan(partf).all() and (partk == -7).all()
     with pytest.raises(ValueError, match="fewer than k"):
         ops.l2h_knn_index(src, bh[:2], bsq[:2], 3)
+    # S = 1 needs no workspace: a null part is accepted and gives the bits of the run with one
+    out2, dist2, idx2 = out.clone(), dist.clone(), idx.clone()
+    assert L.ssad_l2h_knn_fused(*good, None, P(out), 5, 64, 4, 3, 1, st) == 0
+    assert L.ssad_l2h_knn_fused(*good, P(partf), P(out2), 5, 64, 4, 3, 1, st) == 0
+    assert L.ssad_l2h_knn_index(*good, None, P(dist), P(idx), 5, 64, 4, 3, 1, st) == 0
+    assert L.ssad_l2h_knn_index(*good, P(partk), P(dist2), P(idx2), 5, 64, 4, 3, 1, st) == 0
+    torch.cuda.synchronize()
+    assert not torch.isnan(out).any() and (idx >= 0).all()
+    assert torch.equal(out, out2) and torch.equal(dist, dist2) and torch.equal(idx, idx2)
 
 
 # ---------------------------------------------------------------- 6. the detector

@@ -39,9 +39,9 @@ def P(t):
     return None if t is None else t.data_ptr()
 
 
-def std(ins, tail):
-    """The usual argument order: inputs, [workspace], outputs, sizes."""
-    return lambda part, outs: [P(t) for t in ins] + ([] if part is None else [P(part)]) + [P(o) for o in outs] + list(tail)
+def std(ins, tail, null_part=False):
+    """The usual argument order: inputs, [workspace], outputs, sizes.  null_part: a null pointer stands where no workspace is given."""
+    return lambda part, outs: [P(t) for t in ins] + ([P(part)] if part is not None or null_part else []) + [P(o) for o in outs] + list(tail)
 
 
 def run(name, args, out_specs, part_spec=None):
@@ -58,11 +58,11 @@ def run(name, args, out_specs, part_spec=None):
     return [v for _, v in outs], (None if part is None else part[1])
 
 
-def run_both(name, tight, embedded_sets, tail, out_specs, part_spec=None, part_written=False, rows=None, what=()):
+def run_both(name, tight, embedded_sets, tail, out_specs, part_spec=None, part_written=False, rows=None, what=(), null_part=False):
     """`name` on the tight inputs and on every set of embedded ones: the same bits, sane outputs, the workspace written or not."""
-    want, _ = run(name, std(tight, tail), out_specs, part_spec)
+    want, _ = run(name, std(tight, tail, null_part), out_specs, part_spec)
     for v, ins in enumerate(embedded_sets):
-        got, part = run(name, std(ins, tail), out_specs, part_spec)
+        got, part = run(name, std(ins, tail, null_part), out_specs, part_spec)
         for g, w in zip(got, want):
             assert torch.equal(g, w), (name, v) + tuple(what)
             if g.dtype.is_floating_point:
@@ -118,35 +118,38 @@ class Flat:
             self.embedded = [eq + (eb, mu.embedded(bsq, m, m, fill)[1]) for fill in (tsq, mu.BSQ_POISON[bsq.dtype])]
 
 
-FLAT_ENTRIES = {        # kind -> (mean form, index form, their split forms or None, workspace dtypes of the two)
-    "cosine": ("ssad_cosine_knn_fused", "ssad_cosine_knn_index", "ssad_cosine_knn_split", "ssad_cosine_knn_index_split", F32, I64),
-    "l2": ("ssad_l2_knn_fused", "ssad_l2_knn_index", "ssad_l2_knn_split", "ssad_l2_knn_index_split", F32, I64),
-    "half": ("ssad_l2h_knn_fused", "ssad_l2h_knn_index", "ssad_l2h_knn_split", "ssad_l2h_knn_index_split", F32, I64),
-    "int8": (None, None, "ssad_l2q_knn_fused", "ssad_l2q_knn_index", I32, I64),
-    "topk_l2": (None, None, "ssad_l2_knn_topk", "ssad_l2_knn_topk_index", I64, I64),
-    "topk_half": (None, None, "ssad_l2h_knn_topk", "ssad_l2h_knn_topk_index", I64, I64),
+FLAT_ENTRIES = {        # kind -> (mean form, index form, workspace dtypes of the two, mean form of the case without a workspace or None)
+    "cosine": ("ssad_cosine_knn_split", "ssad_cosine_knn_index", F32, I64, "ssad_cosine_knn_fused"),
+    "l2": ("ssad_l2_knn_fused", "ssad_l2_knn_index", F32, I64, "ssad_l2_knn_fused"),
+    "half": ("ssad_l2h_knn_fused", "ssad_l2h_knn_index", F32, I64, "ssad_l2h_knn_fused"),
+    "int8": ("ssad_l2q_knn_fused", "ssad_l2q_knn_index", I32, I64, None),
+    "topk_l2": ("ssad_l2_knn_topk", "ssad_l2_knn_topk_index", I64, I64, None),
+    "topk_half": ("ssad_l2h_knn_topk", "ssad_l2h_knn_topk_index", I64, I64, None),
 }
 # ssad_cosine_knn_split is the two-launch form for every S: its workspace is written for S = 1 too; the others go without it there
 ALWAYS_SPLIT = ("ssad_cosine_knn_split",)
 
 
 def flat_results(c, entries, k):
-    """[(dist, idx, out)] on the host of every (one-launch or split) pair of forms of the case, checked by run_both."""
+    """[(dist, idx, out)] on the host of every (mean, index) pair of runs of the case, checked by run_both: S = 1 without a workspace
+    (a null part; ssad_cosine_knn_fused has neither argument), then every S of mu.SPLITS with one."""
     n, r, d = c.n, c.r, c.d
-    mean1, index1, mean_s, index_s, pdt_mean, pdt_index = entries
+    mean, index, pdt_mean, pdt_index, mean1 = entries
     width = k if c.kind.startswith("topk") else 3
     extra = () if c.s2 is None else (c.s2,)
     mean_spec, index_spec = [((n,), F32)], [((n, k), F32), ((n, k), I32)]
     res = []
     if mean1:
-        (out,) = run_both(mean1, c.tight, c.embedded, (n, d, r, k), mean_spec, what=(n, r, d, k))
-        dist, idx = run_both(index1, c.tight, c.embedded, (n, d, r, k), index_spec, rows=r, what=(n, r, d, k))
+        null = mean1 == mean
+        (out,) = run_both(mean1, c.tight, c.embedded, (n, d, r, k, 1) if null else (n, d, r, k), mean_spec, what=(n, r, d, k),
+                          null_part=null)
+        dist, idx = run_both(index, c.tight, c.embedded, (n, d, r, k, 1), index_spec, rows=r, what=(n, r, d, k), null_part=True)
         res.append((dist, idx, out))
     for s in mu.SPLITS:
         tail = (n, d, r, k, s) + extra
-        (out,) = run_both(mean_s, c.tight, c.embedded, tail, mean_spec, ((s * n, width), pdt_mean), s > 1 or mean_s in ALWAYS_SPLIT,
+        (out,) = run_both(mean, c.tight, c.embedded, tail, mean_spec, ((s * n, width), pdt_mean), s > 1 or mean in ALWAYS_SPLIT,
                           what=(n, r, d, k, s))
-        dist, idx = run_both(index_s, c.tight, c.embedded, tail, index_spec, ((s * n, width), pdt_index), s > 1, rows=r,
+        dist, idx = run_both(index, c.tight, c.embedded, tail, index_spec, ((s * n, width), pdt_index), s > 1, rows=r,
                              what=(n, r, d, k, s))
         res.append((dist, idx, out))
     return res

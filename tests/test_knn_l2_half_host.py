@@ -12,7 +12,7 @@ import knn_l2_half_ref as href
 import knn_l2_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("ssad_rows_to_half", "ssad_l2h_knn_fused", "ssad_l2h_knn_split", "ssad_l2h_knn_index", "ssad_l2h_knn_index_split")
+NEW = ("ssad_rows_to_half", "ssad_l2h_knn_fused", "ssad_l2h_knn_index")
 
 
 def gauss(n, d, seed, mean=0.0):

@@ -1,5 +1,5 @@
 """Time of the gallery kNN kernel (csrc/knn_gallery.hip ssad_l2_knn_gallery) beside the exact Euclidean search of the whole bank
-(csrc/knn_l2.hip ssad_l2_knn_fused / _split) at the shapes of DESIGN §4.16: T = 146 bank images, P = 1024 and 841 rows per image,
+(csrc/knn_l2.hip ssad_l2_knn_fused) at the shapes of DESIGN §4.16: T = 146 bank images, P = 1024 and 841 rows per image,
 D = 384, Q = 1 and 83 query images, K = 10 and 50, k = 3.  With --parent-lib PATH the exact side is the library built from the PARENT
 commit (through ctypes) -- the kernel a user ran before the gallery existed; without it, this build's.  The sides of a row alternate
 inside one loop and the medians of the per-call event times are reported, with the stage-1 prologue (group_means, l2_direct, sort)
@@ -43,20 +43,16 @@ def alternate(fns, reps=15):
 
 
 def exact_kernel(path):
-    """ssad_l2_knn_fused / _split of a build of the library (the parent commit's, or this one's): fn(x, bank, bsq, s)."""
+    """ssad_l2_knn_fused of a build of the library (the parent commit's, or this one's): fn(x, bank, bsq, s)."""
     lib = ctypes.CDLL(path) if path else _hip.lib()
-    for name in ("ssad_l2_knn_fused", "ssad_l2_knn_split"):
-        getattr(lib, name).argtypes = _hip.SIGNATURES[name]
+    lib.ssad_l2_knn_fused.argtypes = _hip.SIGNATURES["ssad_l2_knn_fused"]
 
     def mean(x, bank, bsq, s):
         n, d = x.shape
         out = torch.empty(n, device=dev)
-        if s == 1:
-            rc = lib.ssad_l2_knn_fused(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), out.data_ptr(), n, d, bank.shape[0], 3, _hip.stream())
-        else:
-            part = torch.empty((s, n, 3), device=dev)
-            rc = lib.ssad_l2_knn_split(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), part.data_ptr(), out.data_ptr(), n, d, bank.shape[0],
-                                       3, s, _hip.stream())
+        part = torch.empty((s, n, 3), device=dev) if s > 1 else None
+        rc = lib.ssad_l2_knn_fused(x.data_ptr(), bank.data_ptr(), bsq.data_ptr(), _hip.ptr(part, True), out.data_ptr(), n, d, bank.shape[0],
+                                   3, s, _hip.stream())
         assert rc == 0
     return mean
 

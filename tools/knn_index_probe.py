@@ -1,4 +1,4 @@
-"""Time of the index-returning cosine k-NN (csrc/knn.hip ssad_cosine_knn_index / _split) against the mean kernels it shares its tile
+"""Time of the index-returning cosine k-NN (csrc/knn.hip ssad_cosine_knn_index) against the mean kernels it shares its tile
 with (ssad_cosine_knn_fused / _split) at the shapes of DESIGN §4.8: N = 841 / 13 456 / 70 000 queries, R = 588 / 12 300 / 123 000 bank
 rows, D = 512, k = 3 -- the one-launch forms against each other, and what the ops.knn_splits rule picks for each.  The two sides
 of a pair alternate inside one loop and the medians of the per-call event times are reported.  Then the whole image-score step

@@ -1,5 +1,5 @@
 """Time of the flat Euclidean search with half-precision operands (csrc/knn_l2_half.hip, ops.l2h_knn_fused / l2h_knn_index) against the
-fp32 kernels of the same shape (csrc/knn_l2.hip ssad_l2_knn_fused / _split / _index / _index_split), at the 18 shapes of DESIGN §4.13:
+fp32 kernels of the same shape (csrc/knn_l2.hip ssad_l2_knn_fused / _index), at the 18 shapes of DESIGN §4.13:
 N = 841 / 13 456 / 70 000 queries, R = 588 / 12 300 / 123 000 bank rows, D = 384 and 512, k = 3, and at the pyramid shape (340 000 x
 598 000 rows, D = 448; --pyramid, fewer repetitions).  With --parent-lib PATH the fp32 side is the library built from the PARENT commit
 (through ctypes) -- the kernel a user ran before this option existed; without it, this build's.  The sides of a row alternate inside
@@ -45,20 +45,17 @@ def alternate(fns, reps=15):
 
 
 def fp32_kernels(path):
-    """The four fp32 Euclidean entry points of a build of the library (the parent commit's, or this one's): mean / index fn(x, bank, sq, s)."""
+    """The two fp32 Euclidean entry points of a build of the library (the parent commit's, or this one's): mean / index fn(x, bank, sq, s)."""
     lib = ctypes.CDLL(path) if path else _hip.lib()
-    for name in ("ssad_l2_knn_fused", "ssad_l2_knn_split", "ssad_l2_knn_index", "ssad_l2_knn_index_split"):
+    for name in ("ssad_l2_knn_fused", "ssad_l2_knn_index"):
         getattr(lib, name).argtypes = _hip.SIGNATURES[name]
-    P = lambda t: t.data_ptr()
+    P = lambda t: None if t is None else t.data_ptr()
 
     def mean(x, bank, sq, s):
         n, d = x.shape
         out = torch.empty(n, device=dev)
-        if s == 1:
-            rc = lib.ssad_l2_knn_fused(P(x), P(bank), P(sq), P(out), n, d, bank.shape[0], 3, _hip.stream())
-        else:
-            part = torch.empty((s, n, 3), device=dev)
-            rc = lib.ssad_l2_knn_split(P(x), P(bank), P(sq), P(part), P(out), n, d, bank.shape[0], 3, s, _hip.stream())
+        part = torch.empty((s, n, 3), device=dev) if s > 1 else None
+        rc = lib.ssad_l2_knn_fused(P(x), P(bank), P(sq), P(part), P(out), n, d, bank.shape[0], 3, s, _hip.stream())
         assert rc == 0
         return out
 
@@ -66,11 +63,8 @@ def fp32_kernels(path):
         n, d = x.shape
         dist = torch.empty((n, 3), device=dev)
         idx = torch.empty((n, 3), device=dev, dtype=torch.int32)
-        if s == 1:
-            rc = lib.ssad_l2_knn_index(P(x), P(bank), P(sq), P(dist), P(idx), n, d, bank.shape[0], 3, _hip.stream())
-        else:
-            part = torch.empty((s, n, 3), device=dev, dtype=torch.int64)
-            rc = lib.ssad_l2_knn_index_split(P(x), P(bank), P(sq), P(part), P(dist), P(idx), n, d, bank.shape[0], 3, s, _hip.stream())
+        part = torch.empty((s, n, 3), device=dev, dtype=torch.int64) if s > 1 else None
+        rc = lib.ssad_l2_knn_index(P(x), P(bank), P(sq), P(part), P(dist), P(idx), n, d, bank.shape[0], 3, s, _hip.stream())
         assert rc == 0
         return dist, idx
     return mean, index

@@ -1,4 +1,4 @@
-"""Time of the Euclidean k-NN kernels (csrc/knn_l2.hip ssad_l2_knn_fused / _split / _index / _index_split) against the cosine kernel of
+"""Time of the Euclidean k-NN kernels (csrc/knn_l2.hip ssad_l2_knn_fused / _index) against the cosine kernel of
 the same shape (csrc/knn.hip), at the shapes of DESIGN §4.10: N = 841 / 13 456 / 70 000 queries, R = 588 / 12 300 / 123 000 bank rows,
 D = 384 and 512, k = 3.  With --parent-lib PATH the cosine side is the library built from the PARENT commit (through ctypes) -- the
 kernel a user ran before this metric existed; without it, this build's.  The sides of a row alternate inside one loop and the
@@ -44,9 +44,9 @@ def alternate(fns, reps=15):
 
 
 def cosine_kernels(path):
-    """The four cosine entry points of a build of the library (the parent commit's, or this one's): name -> fn(x, bank, s)."""
+    """The three cosine entry points of a build of the library (the parent commit's, or this one's): name -> fn(x, bank, s)."""
     lib = ctypes.CDLL(path) if path else _hip.lib()
-    for name in ("ssad_cosine_knn_fused", "ssad_cosine_knn_split", "ssad_cosine_knn_index", "ssad_cosine_knn_index_split"):
+    for name in ("ssad_cosine_knn_fused", "ssad_cosine_knn_split", "ssad_cosine_knn_index"):
         getattr(lib, name).argtypes = _hip.SIGNATURES[name]
 
     def mean(x, bank, s):
@@ -64,13 +64,9 @@ def cosine_kernels(path):
         n, d = x.shape
         dist = torch.empty((n, 3), device=dev)
         idx = torch.empty((n, 3), device=dev, dtype=torch.int32)
-        if s == 1:
-            rc = lib.ssad_cosine_knn_index(x.data_ptr(), bank.data_ptr(), dist.data_ptr(), idx.data_ptr(), n, d, bank.shape[0], 3,
-                                           _hip.stream())
-        else:
-            part = torch.empty((s, n, 3), device=dev, dtype=torch.int64)
-            rc = lib.ssad_cosine_knn_index_split(x.data_ptr(), bank.data_ptr(), part.data_ptr(), dist.data_ptr(), idx.data_ptr(), n, d,
-                                                 bank.shape[0], 3, s, _hip.stream())
+        part = torch.empty((s, n, 3), device=dev, dtype=torch.int64) if s > 1 else None
+        rc = lib.ssad_cosine_knn_index(x.data_ptr(), bank.data_ptr(), _hip.ptr(part, True, torch.int64), dist.data_ptr(), idx.data_ptr(), n,
+                                       d, bank.shape[0], 3, s, _hip.stream())
         assert rc == 0
     return mean, index
 

@@ -41,20 +41,17 @@ def alternate(fns, reps):
 
 
 def parent_fp32(path):
-    """ssad_l2_knn_fused / _split and _index / _index_split (k = 3) of another build of the library: fn(x, bank, sq, s)."""
+    """ssad_l2_knn_fused and ssad_l2_knn_index (k = 3) of another build of the library: fn(x, bank, sq, s)."""
     lib = ctypes.CDLL(path)
-    for name in ("ssad_l2_knn_fused", "ssad_l2_knn_split", "ssad_l2_knn_index", "ssad_l2_knn_index_split"):
+    for name in ("ssad_l2_knn_fused", "ssad_l2_knn_index"):
         getattr(lib, name).argtypes = _hip.SIGNATURES[name]
-    P = lambda t: t.data_ptr()
+    P = lambda t: None if t is None else t.data_ptr()
 
     def mean(x, bank, sq, s):
         n, d = x.shape
         out = torch.empty(n, device=dev)
-        if s == 1:
-            rc = lib.ssad_l2_knn_fused(P(x), P(bank), P(sq), P(out), n, d, bank.shape[0], 3, _hip.stream())
-        else:
-            part = torch.empty((s, n, 3), device=dev)
-            rc = lib.ssad_l2_knn_split(P(x), P(bank), P(sq), P(part), P(out), n, d, bank.shape[0], 3, s, _hip.stream())
+        part = torch.empty((s, n, 3), device=dev) if s > 1 else None
+        rc = lib.ssad_l2_knn_fused(P(x), P(bank), P(sq), P(part), P(out), n, d, bank.shape[0], 3, s, _hip.stream())
         assert rc == 0
         return out
 
@@ -62,11 +59,8 @@ def parent_fp32(path):
         n, d = x.shape
         dist = torch.empty((n, 3), device=dev)
         idx = torch.empty((n, 3), device=dev, dtype=torch.int32)
-        if s == 1:
-            rc = lib.ssad_l2_knn_index(P(x), P(bank), P(sq), P(dist), P(idx), n, d, bank.shape[0], 3, _hip.stream())
-        else:
-            part = torch.empty((s, n, 3), device=dev, dtype=torch.int64)
-            rc = lib.ssad_l2_knn_index_split(P(x), P(bank), P(sq), P(part), P(dist), P(idx), n, d, bank.shape[0], 3, s, _hip.stream())
+        part = torch.empty((s, n, 3), device=dev, dtype=torch.int64) if s > 1 else None
+        rc = lib.ssad_l2_knn_index(P(x), P(bank), P(sq), P(part), P(dist), P(idx), n, d, bank.shape[0], 3, s, _hip.stream())
         assert rc == 0
         return dist, idx
     return mean, index
