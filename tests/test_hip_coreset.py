@@ -3,7 +3,6 @@ selection of models.coreset_select, AnomalyDetector(coreset=...) and tools.infer
 
 Integer-valued rows make every fp32 distance exact, so the kernel must then give the selection of a float64 numpy greedy bit for bit
 (ties to the smallest row, early stop); on real-valued rows each pick must be a valid greedy step within fp32 error."""
-import os
 import random
 import time
 
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import two_rank_util
 from coreset_ref import greedy64, replay64
 from fake_mvtec import make_tree
 
@@ -226,25 +226,11 @@ def test_inference_with_coreset(tmp_path, seeded_sd, monkeypatch, capsys):
 
 
 def test_inference_with_coreset_two_ranks_equal_one_rank(tmp_path, seeded_sd):
-    import json
-    import socket
-    import subprocess
-    import sys
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_coreset_worker.py"), str(tmp_path), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "coreset"])
     assert r["maps_equal_across_ranks"], r
     two = torch.load(str(tmp_path / "maps_rank0.pt"))
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train', coreset=0.25)
+    one = two_rank_util.inference(tools, ck, root, "coreset")
     assert torch.equal(two["embeddings"], one.embedding_vectors)
     assert torch.equal(two["maps"], one.anomaly_maps)

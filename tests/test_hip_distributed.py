@@ -3,28 +3,15 @@
 The reference is single-device (tools.py:266); SURVEY s.8e defines the partition.  What is pinned here: replicas start
 from rank 0's state, the reduced gradient equals the sum of the ranks' independently computed gradients, weights stay
 identical across ranks over eager and hipGraph-replayed steps, rank 0 writes the one checkpoint everybody loads."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
+from two_rank_util import launch
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _run(case, tmp, nproc=2, timeout=900):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(HERE, "dist_gpu_worker.py"), case, str(tmp)]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    return json.loads(line[-1][7:])
+def _run(case, tmp, nproc=2):
+    return launch("dist_gpu_worker.py", [case, tmp], nproc=nproc)
 
 
 def test_two_rank_training_step(tmp_path):

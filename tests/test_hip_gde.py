@@ -2,13 +2,13 @@
 
 The reference has no such scorer, so there is no reference vector: the yardstick is numpy / sklearn LedoitWolf / scipy mahalanobis in
 float64 on the same fp32 rows (L2-normalised ones taken from ops.l2_normalize_rows, which both kernels reproduce bit for bit)."""
-import os
 import shutil
 
 import numpy as np
 import pytest
 import torch
 
+import two_rank_util
 from fake_mvtec import make_tree
 
 pytestmark = pytest.mark.gpu
@@ -247,27 +247,9 @@ def test_inference_gde_maps_match_float64(tmp_path, seeded_sd, monkeypatch):
 def test_inference_gde_two_ranks_equal_one_rank(tmp_path, seeded_sd):
     from self_supervised import tools
     root, ck = _seeded_tree(tmp_path, seeded_sd)
-    r = _run_gde(tmp_path, root, ck)
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "gde"])
     assert r["maps_equal_across_ranks"], r
     two = torch.load(str(tmp_path / "maps_rank0.pt"))
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, detector='gde')
+    one = two_rank_util.inference(tools, ck, root, "gde")
     assert torch.equal(two["embeddings"], one.embedding_vectors), "embeddings differ between the 2-rank and 1-rank runs"
     assert torch.equal(two["maps"], one.anomaly_maps)
-
-
-def _run_gde(tmp, root, ck, timeout=900):
-    import json
-    import socket
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_gde_worker.py"), str(tmp), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    return json.loads(line[-1][7:])

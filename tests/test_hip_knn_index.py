@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import knn_index_ref as ref
+import two_rank_util
 from fake_mvtec import make_tree
 
 pytestmark = pytest.mark.gpu
@@ -374,28 +375,13 @@ def test_image_score_argument_errors(tmp_path):
 # ---------------------------------------------------------------- 8. two gloo ranks equal one rank
 
 def test_image_scores_two_ranks_equal_one_rank(tmp_path, seeded_sd):
-    import json
-    import socket
-    import subprocess
-    import sys
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_image_scores_worker.py"), str(tmp_path), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "image_scores"])
     assert r["equal_across_ranks"], r
     two = torch.load(str(tmp_path / "scores_rank0.pt"))
     for mode in ("max", "reweighted"):
-        np.random.seed(3)
-        one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train',
-                              image_scores=mode, neighbours=5)
+        one = two_rank_util.inference(tools, ck, root, "image_scores", run=mode)
         assert tuple(one.image_scores.shape) == (4,)
         assert torch.equal(two[mode]["scores"], one.image_scores)
         assert torch.equal(two[mode]["maps"], one.anomaly_maps)

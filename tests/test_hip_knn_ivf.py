@@ -7,14 +7,13 @@ inputs at the bar tests/knn_l2_ref.py states: a squared distance within 64 units
 one more rounding for the root; rows strict wherever the reference's gaps to both neighbours exceed the bars of both (at most 1 % of
 the (query, slot) pairs are left out, asserted on the reference alone).  Inputs are views between guard rows (NaN, or ids far outside),
 outputs are pre-filled with NaN / -7 and sit between guard rows.  The cells are built by hand: 0, 1, 2, 127, 128, 129 and 300 rows."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import ivf_ref as ref
 import knn_l2_ref as l2ref
+import two_rank_util
 from fake_mvtec import make_tree
 
 pytestmark = pytest.mark.gpu
@@ -545,22 +544,9 @@ def test_inference_with_an_index(tmp_path, seeded_sd, monkeypatch, coreset):
 # ---------------------------------------------------------------- 9. two gloo ranks equal one rank
 
 def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
-    import json
-    import socket
-    import subprocess
-    import sys
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_knn_ivf_worker.py"), str(tmp_path), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "knn_ivf"])
     assert r["equal_across_ranks"] and r["world"] == 2, r
     two = torch.load(str(tmp_path / "ivf_rank0.pt"))
     from self_supervised.models import AnomalyDetector
@@ -571,8 +557,6 @@ def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
         seen["threshold"] = self.threshold
         return orig(self, x)
     monkeypatch.setattr(AnomalyDetector, "predict", spy)
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train',
-                          image_scores='max', metric='euclidean', index='ivf', nprobe=3)
+    one = two_rank_util.inference(tools, ck, root, "knn_ivf")
     assert torch.equal(two["scores"], one.image_scores) and torch.equal(two["maps"], one.anomaly_maps)
     assert two["threshold"] == seen["threshold"] and np.isfinite(seen["threshold"])

@@ -18,6 +18,7 @@ import torch
 
 import coreset_ref
 import knn_l2_ref as ref
+import two_rank_util
 from fake_mvtec import make_tree
 
 pytestmark = pytest.mark.gpu
@@ -651,22 +652,9 @@ def test_sweep_euclidean_writes_its_tables(tmp_path):
 # ---------------------------------------------------------------- 9. two gloo ranks equal one rank
 
 def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
-    import json
-    import socket
-    import subprocess
-    import sys
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_knn_l2_worker.py"), str(tmp_path), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "knn_l2"])
     assert r["equal_across_ranks"] and r["world"] == 2, r
     two = torch.load(str(tmp_path / "l2_rank0.pt"))
     from self_supervised.models import AnomalyDetector
@@ -677,8 +665,6 @@ def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
         seen["threshold"] = self.threshold
         return orig(self, x)
     monkeypatch.setattr(AnomalyDetector, "predict", spy)
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train',
-                          image_scores='reweighted', neighbours=5, metric='euclidean', coreset=0.5)
+    one = two_rank_util.inference(tools, ck, root, "knn_l2")
     assert torch.equal(two["scores"], one.image_scores) and torch.equal(two["maps"], one.anomaly_maps)
     assert two["threshold"] == seen["threshold"] and np.isfinite(seen["threshold"])

@@ -16,8 +16,6 @@ N(10, 1) rows at D = 32 and 384, 2.52 and 3.58 for queries that equal a bank row
 for the flushed rows and 0.25 for the saturated column.  The worst, 3.82, does not exceed the fp32 kernel's 9.77
 (tests/test_hip_knn_l2.py); nothing here says how the instruction orders or rounds its 16 products, only that the result stays this
 close to float64.  tau is 4 x 3.82 = 15.3 -> 16.  The squared norms of ssad_rows_to_half: at most 2.2 units of 2^-24 sum h(x)^2 (bound D + 2)."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -25,6 +23,7 @@ import torch
 import coreset_ref
 import knn_l2_half_ref as href
 import knn_l2_ref as ref
+import two_rank_util
 from fake_mvtec import make_tree
 from knn_paths_util import fp32_rows_held
 
@@ -558,22 +557,9 @@ def test_inference_half_bank(tmp_path, seeded_sd, monkeypatch, localization):
 # ---------------------------------------------------------------- 8. two gloo ranks equal one rank
 
 def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
-    import json
-    import socket
-    import subprocess
-    import sys
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_knn_l2_half_worker.py"), str(tmp_path), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "knn_l2_half"])
     assert r["equal_across_ranks"] and r["world"] == 2, r
     two = torch.load(str(tmp_path / "l2h_rank0.pt"))
     from self_supervised.models import AnomalyDetector
@@ -584,9 +570,7 @@ def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
         seen.update(threshold=self.threshold, bank=self.bank.cpu(), bank_sq=self.bank_sq.cpu())
         return orig(self, x)
     monkeypatch.setattr(AnomalyDetector, "predict", spy)
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train',
-                          image_scores='max', metric='euclidean', coreset=0.5, bank_dtype='float16')
+    one = two_rank_util.inference(tools, ck, root, "knn_l2_half")
     assert torch.equal(two["scores"], one.image_scores) and torch.equal(two["maps"], one.anomaly_maps)
     assert two["bank"].dtype == torch.float16 and torch.equal(two["bank"], seen["bank"]) and torch.equal(two["bank_sq"], seen["bank_sq"])
     assert two["threshold"] == seen["threshold"] and np.isfinite(seen["threshold"])

@@ -10,14 +10,13 @@ form: the bits of the sequential fp32 mean of the index form's own row.
 
 Measured (one run on one MI355X, the tests print it per case): excess at most 1.34 units of 2^-24 of itself (bound D + 2); distances at
 most 0.85 ulp from float64 at every D."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import coreset_ref
 import knn_l2_int8_ref as qref
+import two_rank_util
 from fake_mvtec import make_tree
 from knn_paths_util import fp32_rows_held
 
@@ -529,22 +528,9 @@ def test_inference_int8_bank_equals_the_detector_called_by_hand(tmp_path, seeded
 # ---------------------------------------------------------------- 5. two gloo ranks equal one rank
 
 def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
-    import json
-    import socket
-    import subprocess
-    import sys
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_knn_l2_int8_worker.py"), str(tmp_path), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "knn_l2_int8"])
     assert r["equal_across_ranks"] and r["world"] == 2, r
     two = torch.load(str(tmp_path / "l2q_rank0.pt"))
     from self_supervised.models import AnomalyDetector
@@ -555,9 +541,7 @@ def test_two_ranks_equal_one_rank(tmp_path, seeded_sd, monkeypatch):
         seen.update(threshold=self.threshold, bank=self.bank.cpu(), bank_sq=self.bank_sq.cpu(), quant=self.quant)
         return orig(self, x)
     monkeypatch.setattr(AnomalyDetector, "predict", spy)
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train',
-                          image_scores='max', metric='euclidean', coreset=0.5, bank_dtype='int8')
+    one = two_rank_util.inference(tools, ck, root, "knn_l2_int8")
     assert torch.equal(two["scores"], one.image_scores) and torch.equal(two["maps"], one.anomaly_maps)
     assert two["bank"].dtype == torch.int8 and torch.equal(two["bank"], seen["bank"]) and torch.equal(two["bank_sq"], seen["bank_sq"])
     assert tuple(two["quant"]) == tuple(seen["quant"])

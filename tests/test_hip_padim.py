@@ -2,17 +2,14 @@
 
 The reference has no such scorer: the yardstick is tests/padim_ref.py (numpy.cov + eps I, scipy's mahalanobis, float64).  The bars are
 the project's own: 1e-10 of the magnitudes for the fp64 statistics and 1e-4 relative for the fp32 scores (tests/test_hip_gde.py)."""
-import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import padim_ref as R
+import two_rank_util
 from fake_mvtec import make_tree
 
 pytestmark = pytest.mark.gpu
@@ -399,26 +396,18 @@ def test_padim_sweep_one_category(tree, tmp_path):
 # ------------------------------------------------------------------------------------------------------------------ two ranks
 
 def test_padim_two_ranks_equal_one_rank(tree, tmp_path, monkeypatch):
-    """Two ranks over gloo sharing the one GPU (tests/dist_padim_worker.py): rank 0 fits and broadcasts (state, threshold), the other
-    rank rebuilds the detector from the state -- maps, threshold and image scores are those of the one-rank run, bit for bit."""
+    """Two ranks over gloo sharing the one GPU (tests/dist_inference_worker.py, case padim): rank 0 fits and broadcasts (state,
+    threshold), the other rank rebuilds the detector from the state -- maps, threshold and image scores are those of the one-rank
+    run, bit for bit."""
     from self_supervised import tools
     from self_supervised.density import PositionGaussianDetector
     root, ck = tree
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_padim_worker.py"), str(tmp_path), root, ck, str(CHANNELS)]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    r = json.loads(line[-1][7:])
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "padim", CHANNELS, SIZE])
     assert r["equal_across_ranks"] and r["world"] == 2 and r["shape"] == [4, 1, 12, 12], r
     two = torch.load(str(tmp_path / "padim_rank0.pt"))
     seen = {}
     _spy(monkeypatch, PositionGaussianDetector, seen)
-    one = _run(tools, ck, root, detector='padim', detector_options=OPTS, image_scores='max')
+    one = two_rank_util.inference(tools, ck, root, "padim", channels=CHANNELS)
     assert torch.equal(two["embeddings"], one.embedding_vectors), "embeddings differ between the 2-rank and 1-rank runs"
     assert torch.equal(two["maps"], one.anomaly_maps) and torch.equal(two["image_scores"], one.image_scores)
     assert two["threshold"] == seen["detector"].threshold

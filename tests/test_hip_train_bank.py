@@ -3,12 +3,11 @@ tools.inference(bank='train').
 
 The split kernel must give the bits of ssad_cosine_knn_fused for every split count (min / max selection, same distance expression and
 K order), so that the dispatcher may pick S freely; the float64 yardstick is a numpy brute force of the same rows."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import two_rank_util
 from fake_mvtec import make_tree
 
 pytestmark = pytest.mark.gpu
@@ -221,27 +220,9 @@ def test_train_bank_image_level_gde_matches_sklearn(tmp_path, seeded_sd, monkeyp
 def test_train_bank_two_ranks_equal_one_rank(tmp_path, seeded_sd):
     from self_supervised import tools
     root, ck = _tree(tmp_path, seeded_sd)
-    r = _run_two(tmp_path, root, ck)
+    r = two_rank_util.launch("dist_inference_worker.py", [tmp_path, root, ck, "train_bank"])
     assert r["maps_equal_across_ranks"], r
     two = torch.load(str(tmp_path / "maps_rank0.pt"))
-    np.random.seed(3)
-    one = tools.inference(ck, root + "bottle/", "bottle", mvtec_inference=True, patch_localization=True, bank='train')
+    one = two_rank_util.inference(tools, ck, root, "train_bank")
     assert torch.equal(two["embeddings"], one.embedding_vectors)
     assert torch.equal(two["maps"], one.anomaly_maps)
-
-
-def _run_two(tmp, root, ck, timeout=900):
-    import json
-    import socket
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(here, "dist_train_bank_worker.py"), str(tmp), root, ck]
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-4000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-    assert line, p.stdout[-4000:]
-    return json.loads(line[-1][7:])
