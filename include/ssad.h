@@ -611,6 +611,24 @@ int ssad_l2h_knn_topk(const void* xh, const float* x_sq, const void* bankh, cons
                       int D, int R, int k, int S, void* stream);
 int ssad_l2h_knn_topk_index(const void* xh, const float* x_sq, const void* bankh, const float* bank_sq, void* part, float* dist,
                             int* idx, int64_t N, int D, int R, int k, int S, void* stream);
+/* Refining a coarse shortlist with exact fp32 distances (csrc/knn_refine.hip; faiss' IndexRefineFlat): x [N][D] fp32 queries, bank
+ * [R][D] fp32 rows, cand [N][r] int32 listed bank rows of every query (1 <= r <= 32), any D >= 1.
+ * ssad_rerank_l2_index: for query n the first k (1 <= k <= r) entries of an ascending sort of its listed rows by (d2 bits, bank row,
+ *   place in the list), d2 = sum_c (x_c - b_c)^2 with ssad_l2_direct's bits (lane l of a wave: elements l, l + 64, ... in an fma
+ *   chain, then the xor butterfly) -- they do not depend on N, r, the place in the list or the batch.  dist [N][k] = sqrtf(d2), idx
+ *   [N][k] the bank row.  An entry outside 0 .. R - 1 is skipped; a query with fewer than k valid entries gets (+inf, -1) in the
+ *   missing places; a row listed twice APPEARS TWICE (nothing is deduplicated).
+ * ssad_rerank_l2: out[n] = (dist[n][0] + ... + dist[n][k - 1]) / k, added in that order in fp32 (+inf with fewer than k valid entries).
+ * No atomics, selection by rank counting: the same bits on every call.  Every error returns before a launch, outputs untouched.
+ * ssad_topk_l2q_index: ssad_l2q_knn_index for k = 4..32 (arguments as there; part [S][N][k] 64-bit keys, caller-owned, 8-byte
+ *   aligned, unused for S = 1): idx is exactly the first k entries of a stable ascending sort of (D2, row), D2 the integer squared
+ *   code distance, dist = sqrtf(fmaf(s2, (float)D2, excess)); the first three columns are ssad_l2q_knn_index(k = 3) bit for bit, the
+ *   same bits for every S.  D % 32 == 0, D <= 32768, 4 <= k <= 32, k <= R, codes 16-byte aligned. */
+int ssad_rerank_l2_index(const float* x, const float* bank, const int* cand, float* dist, int* idx, int64_t N, int D, int R, int r,
+                         int k, void* stream);
+int ssad_rerank_l2(const float* x, const float* bank, const int* cand, float* out, int64_t N, int D, int R, int r, int k, void* stream);
+int ssad_topk_l2q_index(const void* xq, const int* x_sq, const float* x_excess, const void* bankq, const int* bank_sq, void* part,
+                            float* dist, int* idx, int64_t N, int D, int R, int k, int S, float s2, void* stream);
 /* SPADE's image-conditioned gallery for the Euclidean kNN (csrc/knn_gallery.hip; Cohen & Hoshen 2020): a query image is scored against
  * the rows of K bank images only.  Queries x [Q P][D] and bank [T P][D] hold P rows per image, image after image.
  * ssad_group_means: out[g][c] = mean_i x[g P + i][c], the image descriptor: summed in fp64 in row order 0 .. P - 1, rounded once to

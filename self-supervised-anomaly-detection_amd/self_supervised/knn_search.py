@@ -19,7 +19,7 @@ def _state(det, **extras):
 
 
 class SearchPath:
-    """What the six paths share.  A subclass supplies ``store``, ``scores`` and ``kneighbors``."""
+    """What the paths share.  A subclass supplies ``store``, ``scores`` and ``kneighbors``."""
 
     def coreset_rows(self, det, train):
         """The fp32 rows a coreset is selected on: the bank where it holds them, else the training rows of ``fit`` once more."""
@@ -155,6 +155,62 @@ class FlatL2Int8(FlatL2):
         return ops.l2q_knn_index(x, det.bank, det.bank_sq, det.quant, k)
 
 
+class Refined:
+    """refine=r on a compressed bank (faiss' IndexRefineFlat): the coarse bank of the class this is mixed into, and beside it
+    `bank_f32`, the same rows as they were.  A query takes the coarse search's min(r, R) nearest rows as a shortlist (``_coarse``: the
+    k <= 3 index kernel, or the list kernel from 4 on) and ranks them again by the direct fp32 distance to `bank_f32`
+    (ops.l2_rerank_mean / l2_rerank_index): every distance returned is that to a real bank row.  `bank_f32` follows the bank through
+    ``store``, ``keep``, ``state`` and ``load``."""
+
+    def _set(self, det, rows) -> None:
+        super()._set(det, rows)
+        det.bank_f32 = rows
+
+    def state(self, det):
+        return dict(super().state(det), refine=det.refine, bank_f32=det.bank_f32.cpu())
+
+    def load(self, det, state) -> None:
+        super().load(det, state)
+        det.bank_f32 = det._dev(state["bank_f32"])
+
+    def _shortlist(self, det, what, x, k):
+        rr = min(det.refine, int(det.bank.shape[0]))
+        if k > rr:
+            raise ValueError(f"{what}: refine={det.refine} on a bank of {int(det.bank.shape[0])} rows gives a shortlist of {rr} rows, "
+                             f"fewer than k = {k}")
+        return self._coarse(det, x, rr)[1]
+
+    def scores(self, det, x):
+        self._check_width("predict", x.shape[1])
+        return ops.l2_rerank_mean(x, det.bank_f32, self._shortlist(det, "predict", x, det.k), det.k)
+
+    def kneighbors(self, det, x, k):
+        return ops.l2_rerank_index(x, det.bank_f32, self._shortlist(det, "kneighbors", x, k), k)
+
+
+class RefinedHalf(Refined, FlatL2Half):
+    """bank_dtype='float16', refine=r: the shortlist comes from l2h_knn_index / l2h_topk_index."""
+
+    def keep(self, det, sel, rows) -> None:
+        super().keep(det, sel, rows)
+        det.bank_f32 = det.bank_f32.index_select(0, sel).contiguous()
+
+    def load(self, det, state) -> None:
+        FlatL2Half._set(self, det, det._dev(state["bank"]))            # the halves again, as FlatL2Half.load; not through Refined._set
+        det.bank_f32 = det._dev(state["bank_f32"])
+
+    def _coarse(self, det, x, r):
+        return FlatL2Half.kneighbors(self, det, x, r)
+
+
+class RefinedInt8(Refined, FlatL2Int8):
+    """bank_dtype='int8', refine=r: the shortlist comes from l2q_knn_index / l2q_topk_index.  ``keep`` codes the kept rows again
+    (FlatL2Int8.keep -> ``_set``), which keeps them as `bank_f32` too."""
+
+    def _coarse(self, det, x, r):
+        return (ops.l2q_topk_index if r > 3 else ops.l2q_knn_index)(x, det.bank, det.bank_sq, det.quant, r)
+
+
 class Gallery(FlatL2):
     """gallery=K: the fp32 bank is made of whole images of `det.patches` rows; `bank_desc` holds their descriptors (recomputed by
     ``load``, and by ``retrieve`` after a bare ``fit_bank``).  k <= 3; image_scores: 'max' and 'retrieval'."""
@@ -243,12 +299,15 @@ class IVF(FlatL2):
 
 _COSINE, _GALLERY, _IVF = Cosine(), Gallery(), IVF()
 _FLAT = {'float32': FlatL2(), 'float16': FlatL2Half(), 'int8': FlatL2Int8()}
+_REFINED = {'float16': RefinedHalf(), 'int8': RefinedInt8()}
 
 
-def choose(metric, index, gallery, bank_dtype) -> SearchPath:
+def choose(metric, index, gallery, bank_dtype, refine=None) -> SearchPath:
     """The path of a detector with these (validated) options."""
     if metric == 'cosine':
         return _COSINE
     if gallery is not None:
         return _GALLERY
+    if refine is not None:
+        return _REFINED[bank_dtype]
     return _IVF if index == 'ivf' else _FLAT[bank_dtype]

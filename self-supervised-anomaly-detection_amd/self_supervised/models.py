@@ -584,6 +584,26 @@ def check_n_neighbors(n_neighbors, metric='cosine', index='flat', gallery=None):
     return int(n_neighbors)
 
 
+REFINE_MIN, REFINE_MAX = 4, 32      # shortlist lengths: below 4 there is nothing to re-rank for k = 3, 32 is ops.RERANK_MAX
+
+
+def check_refine(refine, bank_dtype='float32', n_neighbors=3):
+    """ValueError unless `refine` is None (default: the search of the bank as it is) or an int r in 4..32 that is at least
+    `n_neighbors`, with bank_dtype 'float16' or 'int8' (which already implies metric='euclidean', index='flat' and gallery=None):
+    the compressed search's r nearest rows are ranked again by the direct fp32 distance to the original rows (faiss'
+    IndexRefineFlat; csrc/knn_refine.hip)."""
+    if refine is None:
+        return None
+    if isinstance(refine, (bool, np.bool_)) or not isinstance(refine, (int, np.integer)) or not REFINE_MIN <= refine <= REFINE_MAX:
+        raise ValueError(f"refine must be None or an int in {REFINE_MIN}..{REFINE_MAX} (the length of the shortlist), got {refine!r}")
+    if bank_dtype not in ('float16', 'int8'):
+        raise ValueError(f"refine={refine} needs bank_dtype 'float16' or 'int8' (it ranks a compressed bank's shortlist again on the "
+                         f"fp32 rows; the fp32 bank is searched exactly already), got bank_dtype={bank_dtype!r}")
+    if isinstance(n_neighbors, (int, np.integer)) and not isinstance(n_neighbors, (bool, np.bool_)) and refine < n_neighbors:
+        raise ValueError(f"refine={refine} must be at least n_neighbors={n_neighbors}: the k nearest are taken from the shortlist")
+    return int(refine)
+
+
 INDEXES = ('flat', 'ivf')
 IVF_OPTIONS = ('iters', 'seed', 'train_rows')
 IVF_MAX_NLIST = 4096
@@ -684,6 +704,16 @@ class AnomalyDetector(Detector):
     to [lo, hi] took from the query (ops.l2q_knn_fused / l2q_knn_index): it differs from the fp32 distance by at most s sqrt(D) for
     a query inside the bank's range and never exceeds it by more.  Same conditions as 'float16', and n_neighbors in 1..3.
 
+    `refine` (opt-in, with bank_dtype 'float16' or 'int8'; faiss' IndexRefineFlat): None (default) = the compressed search's answer;
+    an int r in 4..32, at least n_neighbors = the compressed search returns its r' = min(r, R) nearest rows as a SHORTLIST
+    (ops.l2h_topk_index / l2q_topk_index; the k <= 3 index kernels for r' <= 3) and the score and ``kneighbors`` are taken from the
+    direct fp32 distances sum (x - b)^2 of the query to those rows of `bank_f32`, the rows before rounding or coding, kept beside
+    the compressed bank (4 D bytes per row more) -- ops.l2_rerank_mean / l2_rerank_index, csrc/knn_refine.hip.  Every distance
+    returned is the direct fp32 distance to a real bank row, so a refined score is never below the exact search's (up to the direct
+    form's rounding); it EQUALS the exact k nearest whenever they all are in the shortlist, and always when R <= r.  It does not
+    promise the fp32 flat kernel's bits: that kernel uses the expanded form |x|^2 + |b|^2 - 2 <x, b>, the direct form is the more
+    accurate of the two.  ``kneighbors`` takes k <= r'.  A state carries `refine` and `bank_f32`.
+
     `n_neighbors` (default 3, the reference's; sklearn's n_neighbors, PatchCore's anomaly_scorer_num_nn, SPADE's kappa): the k of the
     score -- the mean distance to the k nearest bank rows -- kept as `self.k` and read by ``predict``, the threshold of ``fit``, the
     patch scores inside ``image_scores`` and the default of ``kneighbors``.  1..3 run on every path with the kernels those paths
@@ -692,9 +722,12 @@ class AnomalyDetector(Detector):
     Cosine, gallery and IVF searches for k > 3 are a follow-up.  A bank of fewer rows than n_neighbors raises.  Not to be confused
     with the `neighbours` of ``image_scores``: that is the b of PatchCore's eq. 6-7, the size of the reweighting neighbourhood."""
 
+    refine = None       # the shortlist length of a refined detector; an instance attribute only where the option is set
+
     def __init__(self, patch_level: bool = False, batch: int = None, num_patches: int = None, coreset=None,
                  coreset_dim: int = 128, metric: str = 'cosine', index: str = 'flat', nlist: int = None, nprobe: int = 8,
-                 index_options: dict = None, bank_dtype: str = 'float32', n_neighbors: int = 3, gallery: int = None) -> None:
+                 index_options: dict = None, bank_dtype: str = 'float32', n_neighbors: int = 3, refine: int = None,
+                 gallery: int = None) -> None:
         super().__init__(patch_level, batch, num_patches)
         self.bank = None
         self.bank_sq = None             # metric='euclidean': squared norms of the bank rows (ops.row_sqnorms)
@@ -719,7 +752,12 @@ class AnomalyDetector(Detector):
         if self.bank_dtype == 'int8':
             self.quant = None           # after fit: (lo, s) of the bank's 8-bit code (ops.int8_quantiser)
         # how the bank is kept and searched: everything below delegates to it (knn_search.py); the data stays in the attributes above
-        self._search = knn_search.choose(self.metric, self.index, self.gallery, self.bank_dtype)
+        if check_refine(refine, self.bank_dtype, self.k) is None:
+            self._search = knn_search.choose(self.metric, self.index, self.gallery, self.bank_dtype)
+        else:                           # the default detector carries nothing of the option (`refine` is then the class's None)
+            self.refine = int(refine)
+            self.bank_f32 = None        # after fit: the fp32 rows of the compressed bank, what the shortlist is ranked on again
+            self._search = knn_search.choose(self.metric, self.index, self.gallery, self.bank_dtype, self.refine)
 
     @property
     def n_neighbors(self) -> int:
@@ -792,6 +830,8 @@ class AnomalyDetector(Detector):
         if state.get("n_neighbors", 3) != self.n_neighbors:
             raise ValueError(f"load_state: the bank was fitted with n_neighbors={state.get('n_neighbors', 3)!r}, this detector has "
                              f"{self.n_neighbors!r}")
+        if state.get("refine") != self.refine:
+            raise ValueError(f"load_state: the bank was fitted with refine={state.get('refine')!r}, this detector has {self.refine!r}")
         if ("nlist" in state) != (self.index == 'ivf'):
             raise ValueError(f"load_state: the bank was fitted with index={'ivf' if 'nlist' in state else 'flat'!r}, this detector has "
                              f"{self.index!r}")

@@ -1097,6 +1097,75 @@ def l2h_topk_mean(x, bank_h, bank_sq, k, splits=None):
     return out
 
 
+def l2q_topk_index(x, bank_q, bank_sq, quant, k, splits=None):
+    """l2q_knn_index for k in 4..32 (arguments as l2q_knn_fused; csrc/knn_refine.hip ssad_topk_l2q_index): (dist [N][k] float32,
+    idx [N][k] int32), exactly the first k entries of a stable ascending sort of the (D2, bank row) pairs between the codes; a pair's
+    dist has l2q_knn_index's bits, so the first three columns are l2q_knn_index(k=3).  The same bits for every S and every batch."""
+    _check_int8_width("l2q_topk_index", x.shape[1])
+    n, d, r, k, s = _l2_flat_args("l2q_topk_index", x, bank_q, bank_sq, k, splits, torch.int8, (TOPK_MIN, TOPK_MAX))
+    lo = float(np.float32(quant[0]))
+    if not np.isfinite(lo):
+        raise ValueError(f"l2q_topk_index: quant = (lo, s) must be finite, got {tuple(quant)!r}")
+    step, inv_s, s2 = _int8_from_step(quant[1])
+    xq, xsq, xex = rows_to_int8(x, lo, inv_s, step)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    part = torch.empty((s, n, k), device=x.device, dtype=torch.int64) if s > 1 else None     # (D2 << 32 | row) keys
+    i8, i32 = torch.int8, torch.int32
+    _run("l2q_topk_index", 2.0 * n * d * r, 1.0 * (x.numel() + bank_q.numel()) + 4.0 * (r + 2 * n + 2 * n * k) + 16.0 * (s > 1) * s * n * k,
+         lambda: _hip.lib().ssad_topk_l2q_index(_hip.ptr(xq, dtype=i8), _hip.ptr(xsq, dtype=i32), _hip.ptr(xex),
+                                                    _hip.ptr(bank_q, dtype=i8), _hip.ptr(bank_sq, dtype=i32),
+                                                    _hip.ptr(part, True, torch.int64), _hip.ptr(dist), _hip.ptr(idx, dtype=i32), n, d, r,
+                                                    k, s, s2, _hip.stream()))
+    return dist, idx
+
+
+RERANK_MAX = 32     # the longest shortlist of csrc/knn_refine.hip (TOPK_MAX: what the coarse searches return)
+
+
+def _rerank_args(name, x, bank, cand, k):
+    """The argument checks of the re-rank, from shapes and dtypes alone: fp32 x [N][D] and bank [R][D], int32 cand [N][r] with r in
+    1..RERANK_MAX, k in 1..r.  -> (n, d, rows, r, k)."""
+    if x.dim() != 2 or bank.dim() != 2 or x.dtype != torch.float32 or bank.dtype != torch.float32 or bank.shape[1] != x.shape[1] \
+            or x.shape[0] < 1 or x.shape[1] < 1 or bank.shape[0] < 1:
+        raise ValueError(f"{name}: x [N][D] and bank [R][D] must be float32 of one width, got {x.dtype} {tuple(x.shape)} and "
+                         f"{bank.dtype} {tuple(bank.shape)}")
+    n, d = x.shape
+    if cand.dim() != 2 or cand.dtype != torch.int32 or cand.shape[0] != n:
+        raise ValueError(f"{name}: cand must be int32 [{n}][r], got {cand.dtype} {tuple(cand.shape)}")
+    r, k = int(cand.shape[1]), int(k)
+    if not 1 <= r <= RERANK_MAX:
+        raise ValueError(f"{name}: a shortlist holds 1..{RERANK_MAX} rows, got r = {r}")
+    if not 1 <= k <= r:
+        raise ValueError(f"{name}: k must lie in 1..r = 1..{r}, got {k}")
+    return n, d, int(bank.shape[0]), r, k
+
+
+def l2_rerank_index(x, bank, cand, k):
+    """x [N][D], bank [R][D] fp32, cand [N][r] int32 listed bank rows (r in 1..32) -> (dist [N][k] float32, idx [N][k] int32): the k
+    (1..r) nearest of every query's listed rows by the direct squared distance sum (x - b)^2 -- l2_direct's bits for the pair --
+    ascending by (d2, bank row, place in the list); dist holds the roots (csrc/knn_refine.hip ssad_rerank_l2_index).  An entry
+    outside 0..R-1 is skipped, missing places are (+inf, -1), a row listed twice appears twice."""
+    n, d, rows, r, k = _rerank_args("l2_rerank_index", x, bank, cand, k)
+    dist = _new((n, k), x)
+    idx = torch.empty((n, k), device=x.device, dtype=torch.int32)
+    _run("l2_rerank_index", 3.0 * n * r * d, 4.0 * (x.numel() + n * r * d + n * r + 2 * n * k),
+         lambda: _hip.lib().ssad_rerank_l2_index(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(cand, dtype=torch.int32), _hip.ptr(dist),
+                                                 _hip.ptr(idx, dtype=torch.int32), n, d, rows, r, k, _hip.stream()))
+    return dist, idx
+
+
+def l2_rerank_mean(x, bank, cand, k):
+    """-> [N] the sequential fp32 sum of l2_rerank_index's dist row, smallest first, divided by k (csrc/knn_refine.hip
+    ssad_rerank_l2): +inf for a query with fewer than k valid entries."""
+    n, d, rows, r, k = _rerank_args("l2_rerank_mean", x, bank, cand, k)
+    out = _new((n,), x)
+    _run("l2_rerank_mean", 3.0 * n * r * d, 4.0 * (x.numel() + n * r * d + n * r + n),
+         lambda: _hip.lib().ssad_rerank_l2(_hip.ptr(x), _hip.ptr(bank), _hip.ptr(cand, dtype=torch.int32), _hip.ptr(out), n, d, rows, r,
+                                           k, _hip.stream()))
+    return out
+
+
 def l2_from_dots(sim, qsq, bsq):
     """sim [Q][R] dot products, qsq [Q], bsq [R] squared norms -> [Q][R] SQUARED Euclidean distances max(qsq + bsq - 2 sim, 0)
     (csrc/knn_l2.hip ssad_l2_from_dots; the kNN kernels' expression)."""

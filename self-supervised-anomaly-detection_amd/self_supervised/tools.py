@@ -448,6 +448,14 @@ def _check_n_neighbors(n_neighbors, detector, metric, index, gallery):
     return models.check_n_neighbors(n_neighbors, metric, index, gallery)
 
 
+def _check_refine(refine, detector, bank_dtype, n_neighbors):
+    """The refine option of the kNN detector (models.check_refine; faiss' IndexRefineFlat): the r nearest rows of the fp16 / int8
+    search ranked again by their direct fp32 distances; r in 4..32, at least n_neighbors."""
+    if refine is not None and detector != 'knn':
+        raise ValueError(f"refine={refine!r} applies to detector='knn' only, got detector={detector!r}")
+    return models.check_refine(refine, bank_dtype, n_neighbors)
+
+
 def _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery=None, index='flat'):
     """The image-score option (models.check_image_scores): patch level and the kNN detector only -- the score is taken from the patch
     scores and their nearest bank rows, which the image level and the Gaussian do not have."""
@@ -527,7 +535,7 @@ def _pyramid_columns(detector, det_kw):
 
 def _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores, neighbours, options,
                    gallery=None, dense_features='local', index='flat', nlist=None, nprobe=8, index_options=None, bank_dtype='float32',
-                   n_neighbors=3):
+                   n_neighbors=3, refine=None):
     """Every option check of `inference` and `sweep`, from the arguments alone; returns the detector's class and constructor arguments."""
     _check_detector(detector)
     _check_metric(metric, detector)
@@ -540,6 +548,7 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
     _check_image_scores(image_scores, neighbours, patch_localization, detector, gallery, index)
     _check_bank_dtype(bank_dtype, detector, metric, index, gallery, image_scores, n_neighbors)
     n_neighbors = _check_n_neighbors(n_neighbors, detector, metric, index, gallery)
+    refine = _check_refine(refine, detector, bank_dtype, n_neighbors)
     det_kw = _check_padim(detector, patch_localization, localization, bank, options)
     if dense_features == 'pyramid' and detector == 'padim':
         det_kw.update(preselected=True, width=PYRAMID_WIDTH)     # the model writes the chosen columns only (_pyramid_columns)
@@ -556,6 +565,8 @@ def _check_options(detector, metric, localization, patch_localization, bank, mvt
         det_kw["bank_dtype"] = bank_dtype
     if n_neighbors != 3:
         det_kw["n_neighbors"] = n_neighbors
+    if refine is not None:
+        det_kw["refine"] = refine
     return models.DETECTORS[detector], det_kw
 
 
@@ -761,7 +772,7 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
               localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine',
               dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
               index_options: dict = None, bank_dtype: str = 'float32', n_neighbors: int = 3,
-              gallery: int = None) -> ModelOutputsContainer:
+              refine: int = None, gallery: int = None) -> ModelOutputsContainer:
     """tools.py:310-390.  `detector`: 'knn' = the reference's cosine 3-NN (AnomalyDetector), 'gde' = the Gaussian density
     estimator of CutPaste (GaussianDensityDetector: Ledoit-Wolf Gaussian, Mahalanobis distance; needs >= 2 fit rows).
     `bank`: what the detector is fitted on.  'reference' (default) = the reference's: ONE training image drawn by a shuffled loader
@@ -808,10 +819,15 @@ def inference(model_input_dir: str, dataset_dir: str, subject: str, mvtec_infere
     `n_neighbors`: the k of the kNN score (AnomalyDetector(n_neighbors=k); sklearn's n_neighbors, PatchCore's anomaly_scorer_num_nn,
     SPADE's kappa), default 3 as the reference: maps, threshold and the patch scores under `image_scores` are the mean distance to
     the k nearest bank rows.  1..3 on every path; 4..32 need metric='euclidean', index='flat' and gallery=None (either bank_dtype).
-    'knn' only.  Not the `neighbours` above, which sizes the reweighting neighbourhood of image_scores='reweighted'."""
+    'knn' only.  Not the `neighbours` above, which sizes the reweighting neighbourhood of image_scores='reweighted'.
+    `refine`: None (default) = the answer of the search as it is; an int r in 4..32, at least n_neighbors, with bank_dtype 'float16' or
+    'int8' (AnomalyDetector(refine=r); faiss' IndexRefineFlat) = the compressed search's r nearest rows are ranked again by their
+    direct fp32 distances to the original rows, which the bank then keeps beside the compressed ones (4 D bytes per row more, on every
+    rank and in the broadcast): every score is the mean of direct fp32 distances to real bank rows, equal to the exact search's
+    whenever its k nearest are all in the shortlist."""
     cls, det_kw = _check_options(detector, metric, localization, patch_localization, bank, mvtec_inference, coreset, image_scores,
                                  neighbours, detector_options, gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype,
-                                 n_neighbors)
+                                 n_neighbors, refine)
     del TIMELINE[:]
     print('>>> initializing inference')
     plan = _plan_inputs(dataset_dir, mvtec_inference, bank == 'train')
@@ -952,13 +968,13 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
           localization: str = 'patches', detector_options: dict = None, metric: str = 'cosine', upsample_method: str = 'reference',
           upsample_sigma: float = 4.0, dense_features: str = 'local', index: str = 'flat', nlist: int = None, nprobe: int = 8,
           index_options: dict = None, bank_dtype: str = 'float32', average_precision: bool = False, n_neighbors: int = 3,
-          gallery: int = None):
+          refine: int = None, gallery: int = None):
     """Category sweep (BASELINE configs[4]; the loop of src/evaluator.py:432-564 without its plots): per category
     training -> inference -> upsample -> Evaluator, one row of scores each plus an 'average' row, exported as csv /
     markdown when `tables_output` is given.  Categories are independent models: under torch.distributed (one process per
     GPU) rank r takes categories r, r + world, ... and the rows are exchanged once at the end -- no collective inside a
     category.  Returns the pandas DataFrame (identical on every rank).  `detector`, `bank`, `coreset`, `image_scores`,
-    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe`, `index_options`, `bank_dtype` and `n_neighbors` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
+    `neighbours`, `localization`, `detector_options`, `metric`, `gallery`, `dense_features`, `index`, `nlist`, `nprobe`, `index_options`, `bank_dtype`, `n_neighbors` and `refine` as in `inference`; with `image_scores` set, the image AUROC of the patch-level model (image_auroc) goes into one
     more table, patch_image_auroc.csv -- the reference-layout tables and the returned frame keep their columns.
     `upsample_method` and `upsample_sigma` go to the one `upsample` call ('resize_blur': PatchCore's / PaDiM's maps).
     `average_precision=True` (patch level) writes one more table in the same way, patch_ap.csv: the pixel AP of the upsampled maps
@@ -966,7 +982,7 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
     if upsample_method not in ('reference', 'resize_blur'):
         raise ValueError(f"sweep: upsample_method is 'reference' or 'resize_blur', got {upsample_method!r}")
     _check_options(detector, metric, localization, patch_localization, bank, True, coreset, image_scores, neighbours, detector_options,
-                   gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype, n_neighbors)
+                   gallery, dense_features, index, nlist, nprobe, index_options, bank_dtype, n_neighbors, refine)
     if average_precision and not patch_localization:
         raise ValueError("sweep: average_precision=True needs patch_localization=True (patch_ap.csv holds the pixel AP)")
     rank, world = world_info()
@@ -989,6 +1005,8 @@ def sweep(dataset_dir: str, outputs_dir: str, categories: list, imsize: tuple = 
         score_kw["bank_dtype"] = bank_dtype
     if n_neighbors != 3:
         score_kw["n_neighbors"] = n_neighbors
+    if refine is not None:
+        score_kw["refine"] = refine
     for subject in mine:
         sub_out = os.path.join(outputs_dir, subject) + '/'
         data = os.path.join(dataset_dir, subject) + '/'
